@@ -13,8 +13,18 @@ at N>1 plus one RCCL all-reduce of all gradients (weak scaling: every rank
 renders its own 8192 rays).  Optimizer / density-grid update excluded, as in
 the metric definition.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints one JSON line:
+the headline `value`, `ms_per_step` and the roofline of the kernel that is
+bracketed by events inside the timed region.  `--dump-outputs DIR` writes what
+the last timed step returned (per-ray outputs and the three gradients) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by
+array.  `--full` adds every other leg after the timed region: the per-kernel
+breakdown, forward-only, train / drop-in / API steps, density update,
+test-time render, the N > 1 step without its collectives, and the CPU-oracle
+legs (rgb check, CPU baseline).
 
 `--gpus N` without a torchrun environment starts the N ranks itself (a
 `torch.distributed.run` child process, before this process touches the GPU)
@@ -95,6 +105,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg (per-kernel "
+                         "breakdown, forward-only, train / drop-in / API steps, density update, "
+                         "test-time render, CPU-oracle rgb check and CPU baseline); a plain run "
+                         "times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rgb, opacity, depth, gate "
+                         "weights, grid / MLP / gate gradients) as DIR/<name>.npy, float32")
     ap.add_argument("--rays", type=int, default=8192, help="rays per GPU")
     ap.add_argument("--models", type=int, default=2)
     ap.add_argument("--scale", type=float, default=0.5)
@@ -263,6 +281,34 @@ def launch_check(args, rank, local, world):
         dist.destroy_process_group()
 
 
+DUMP_BUDGET = 60 << 20       # bytes of .npy payload per --dump-outputs directory
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: every tensor as <path>/<name>.npy in float32.  All of
+    them whole when they fit DUMP_BUDGET together; otherwise the arrays over
+    1 MiB share what the small ones leave, and one larger than its share is
+    saved as a fixed sample (elements at seeded, sorted flat indices, the same
+    for every run of the same shape).  Returns {name: [shape, elements saved]}."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy())
+              for k, v in tensors.items() if v is not None}
+    big = [k for k, a in arrays.items() if a.nbytes > 1 << 20]
+    share = None
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET:
+        small = sum(a.nbytes for k, a in arrays.items() if k not in big)
+        share = (DUMP_BUDGET - small) // len(big) // 4
+    saved = {}
+    for k, a in arrays.items():
+        shape = list(a.shape)
+        if share is not None and k in big and a.size > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        saved[k] = [shape, int(a.size)]
+    return saved
+
+
 def main():
     args = parse()
     rc = self_launch(args)
@@ -378,10 +424,12 @@ def main():
     r.after_field_bwd = early_bucket
     # (one rank: no collective to overlap, the fold sums every level in one launch)
     r.after_grid_levels = grid_levels_ready if world > 1 else None
+    last = [None]                   # what the latest step's forward returned
 
     def step(i):
         ar.zero()
-        _, _, _, gt, _ = r.forward(rays_o, rays_d, rays_d, noises[i % 4], bg, 1e-4, esf)
+        rgb, opacity, depth, gt, _ = r.forward(rays_o, rays_d, rays_d, noises[i % 4], bg, 1e-4, esf)
+        last[0] = (rgb, opacity, depth, gt)
         samples_acc.add_(r.ws.meta[1])
         grid_early[0] = None
         r.backward(rays_o, rays_d, rays_d, gt, bg, g_rgb, g_op, g_depth, None, 1e-4,
@@ -423,11 +471,20 @@ def main():
     elapsed = time.perf_counter() - t0
     live = r.kernel_times_ms()
     bwd_live = live["field_bwd"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step: the renderer's outputs and the gradients its
+        # backward (and, N > 1, the all-reduce) left in the flat buffer
+        names = ("rgb", "opacity", "depth", "gate")
+        dumped = dump_outputs(args.dump_outputs, dict(
+            zip(names, last[0]), grid_grad=ar.views[0], mlp_grad=ar.views[1],
+            gate_grad=ar.views[2]))
     comm = None
     if world > 1:
+        comm = ar.comm_stats(args.steps)
+    if world > 1 and args.full:
         # the collectives of the timed steps, then the same steps without them:
         # exposed = what the all-reduce adds to the step (max over ranks)
-        comm = ar.comm_stats(args.steps)
         comm_on[0] = False
         dist.barrier()
         torch.cuda.synchronize()
@@ -453,57 +510,59 @@ def main():
                          if early_ok else
                          f"gloo: MLP+gate bucket and the grid in {args.buckets} buckets after the "
                          "backward (host-blocking collectives); comm stream events")})
-    # per-kernel breakdown: the same steps again with every launch traced
-    # (after the timed region; not part of `value`)
-    r.trace = True
-    r.events = {}
-    saved = samples_acc.clone()
-    for i in range(args.steps):
-        step(i)
-    samples_acc.copy_(saved)
-    r.trace = False
-    kt = r.kernel_times_ms()
-    kt["field_bwd"] = bwd_live
-    for k_ in ("fx_bin", "fx_sum"):             # the binned fold, timed in the headline region
-        if k_ in live:
-            kt[k_] = live[k_]
-    # gate_bwd runs on a side stream beside field_bwd (hidden there, but its
-    # events then span the wait for CUs): its own duration, in line
-    at = r.gate_bwd_at
-    r.gate_bwd_at, r.trace, r.events = "main", {"gate_bwd"}, {}
-    for i in range(3):
-        step(i)
-    samples_acc.copy_(saved)
-    r.gate_bwd_at, r.trace = at, False
-    gt_ms = r.kernel_times_ms().get("gate_bwd")
-    if gt_ms:                       # (one sub-NeRF: no gate MLP at all)
-        kt["gate_bwd"] = gt_ms
+    kt, fwd_only = live, None
+    if args.full:
+        # per-kernel breakdown: the same steps again with every launch traced
+        # (after the timed region; not part of `value`)
+        r.trace = True
+        r.events = {}
+        saved = samples_acc.clone()
+        for i in range(args.steps):
+            step(i)
+        samples_acc.copy_(saved)
+        r.trace = False
+        kt = r.kernel_times_ms()
+        kt["field_bwd"] = bwd_live
+        for k_ in ("fx_bin", "fx_sum"):             # the binned fold, timed in the headline region
+            if k_ in live:
+                kt[k_] = live[k_]
+        # gate_bwd runs on a side stream beside field_bwd (hidden there, but its
+        # events then span the wait for CUs): its own duration, in line
+        at = r.gate_bwd_at
+        r.gate_bwd_at, r.trace, r.events = "main", {"gate_bwd"}, {}
+        for i in range(3):
+            step(i)
+        samples_acc.copy_(saved)
+        r.gate_bwd_at, r.trace = at, False
+        gt_ms = r.kernel_times_ms().get("gate_bwd")
+        if gt_ms:                       # (one sub-NeRF: no gate MLP at all)
+            kt["gate_bwd"] = gt_ms
 
-    # forward-only rate (north_star's forward target), timed after the headline
-    # region with the same barrier/sync bracketing; not part of `value`
-    fwd_acc = torch.zeros((), dtype=torch.int64, device=dev)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        r.forward(rays_o, rays_d, rays_d, noises[i % 4], bg, 1e-4, esf)
-        fwd_acc.add_(r.ws.meta[1])
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    fwd_elapsed = torch.tensor(time.perf_counter() - t0, device=dev, dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(fwd_acc)
-        dist.all_reduce(fwd_elapsed, op=dist.ReduceOp.MAX)
-    fwd_only = {"value": round(int(fwd_acc) / float(fwd_elapsed) / 1e6, 2), "unit": "Msamples/s",
-                "ms_per_step": round(float(fwd_elapsed) / args.steps * 1e3, 4)}
+        # forward-only rate (north_star's forward target), timed after the headline
+        # region with the same barrier/sync bracketing; not part of `value`
+        fwd_acc = torch.zeros((), dtype=torch.int64, device=dev)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            r.forward(rays_o, rays_d, rays_d, noises[i % 4], bg, 1e-4, esf)
+            fwd_acc.add_(r.ws.meta[1])
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        fwd_elapsed = torch.tensor(time.perf_counter() - t0, device=dev, dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(fwd_acc)
+            dist.all_reduce(fwd_elapsed, op=dist.ReduceOp.MAX)
+        fwd_only = {"value": round(int(fwd_acc) / float(fwd_elapsed) / 1e6, 2), "unit": "Msamples/s",
+                    "ms_per_step": round(float(fwd_elapsed) / args.steps * 1e3, 4)}
 
     # full training step of train_ml.py: render ->
     # fused NeRFLoss (opacity 1e-3, CV^2 1e-2, depth-mutual 5e-2) -> backward ->
     # (all-reduce) -> FusedAdam; synthetic target colours.  Not part of `value`.
     train = None
-    if args.train_step:
+    if args.full and args.train_step:
         log("train step leg")
         from radnerf_amd.optim import FusedAdam
         params = [model.xyz_encoder.params, model.mlp_params, gate.params]
@@ -546,7 +605,7 @@ def main():
     # same kernels), for the callers that keep ml_rendering.py; rank 0 at N=1.
     # Same rays and noise cycle as the headline, so the same samples per step.
     dropin, api_step = None, None
-    if args.dropin_step and world == 1:
+    if args.full and args.dropin_step and world == 1:
         log("drop-in / API legs")
         from radnerf_amd.rendering import ml_render, render
 
@@ -590,7 +649,7 @@ def main():
     # 128^3 x cascades cells of every sub-NeRF, and the regular update over
     # 128^3/4 uniform + 128^3/4 occupied cells, rank-consistent stream
     density = None
-    if args.density_update:
+    if args.full and args.density_update:
         log("density-update leg")
         thr = 0.01 * 1024 / 3 ** 0.5
         dms = {}
@@ -615,7 +674,7 @@ def main():
     # test-time render (row a10, ml_rendering.py:81-155): one image of
     # --test-time-rays rays through ml_render(test_time=True); not part of `value`
     test_time = None
-    if args.test_time_rays and world == 1:
+    if args.full and args.test_time_rays and world == 1:
         log("test-time render leg")
         from radnerf_amd.rendering import ml_render
         nt = args.test_time_rays
@@ -749,7 +808,7 @@ def main():
 
     rgb_linf = None
     cpu_base = None
-    if rank == 0 and world == 1 and args.cpu_rays > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_rays > 0:
         log("oracle legs (rgb check, CPU baseline)")
         rgb_linf, cpu_base = oracle_legs(args, model, gate, bits, o_np, d_np, noises[0], r,
                                          rays_o, rays_d, bg, esf, scale, seeds_np)
@@ -773,7 +832,7 @@ def main():
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
                "scaling": "strong" if args.pinned else "weak", "vs_baseline": None,
-               "dtype": "f16/f32",
+               "dtype": "f16/f32", "full": bool(args.full), "outputs": dumped,
                "data": "synthetic",
                "backend": dist.get_backend() if world > 1 else None,
                "comm": comm,
