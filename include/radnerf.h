@@ -172,6 +172,30 @@ int rn_ml_composite_bw(const float* dL_drgb, const float* dL_dopacity, const flo
                        const float* depth_k, const float* rgb_k, int64_t n_rays,
                        int32_t n_models, float T_threshold, float* dL_dsigmas, float* dL_drgbs,
                        void* stream);
+/* the same with the Mip-NeRF 360 distortion loss of every (model, ray) segment
+ * in the chain (losses.cu:47-142, losses.py:6-36 DistortionLoss per sub-NeRF
+ * as NeRFLoss applies it, losses.py:63-67), without the ws_incl / wts_incl /
+ * dL_dws arrays of rn_distortion_loss_fw / _bw:
+ * fw also writes dist_k [K][B], the loss of the segment's ws (every other
+ *   output is rn_ml_composite_fw's, bit for bit);
+ * bw adds the loss's gradient for the seed dL_ddist [K][B] -- or, when that is
+ *   NULL, the constant dL_ddist_const for every segment -- to dL_dsigmas, as
+ *   VolumeRenderer.backward does with dL_dws (volumerendering.cu:109-151); it
+ *   reads the ws and dist_k the forward wrote.  No gradient reaches ts /
+ *   deltas (losses.py:36 returns None there).                               */
+int rn_ml_composite_dist_fw(const float* sigmas, const float* rgbs, const float* deltas,
+                            const float* ts, const int32_t* counts, const int32_t* offsets,
+                            int64_t n_rays, int32_t n_models, float T_threshold, int32_t* used,
+                            float* opacity_k, float* depth_k, float* rgb_k, float* ws,
+                            float* dist_k, void* stream);
+int rn_ml_composite_dist_bw(const float* dL_drgb, const float* dL_dopacity,
+                            const float* dL_ddepth, const float* dL_ddist, float dL_ddist_const,
+                            const float* gate, const float* bg, const float* sigmas,
+                            const float* rgbs, const float* deltas, const float* ts,
+                            const float* ws, const int32_t* counts, const int32_t* offsets,
+                            const float* opacity_k, const float* depth_k, const float* rgb_k,
+                            const float* dist_k, int64_t n_rays, int32_t n_models,
+                            float T_threshold, float* dL_dsigmas, float* dL_drgbs, void* stream);
 
 /* ---- field: shared hash grid + per-model geo/rgb MLP -----------------------
  * replaces MNGP.forward / tcnn Encoding+Network fwd/bwd

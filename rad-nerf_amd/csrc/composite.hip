@@ -31,12 +31,23 @@ __device__ __forceinline__ int seg_break(const float* __restrict__ sig,
 
 // Forward over one segment.  All lanes of the wave call this with the same
 // (start, n).  Writes ws for the samples that contribute (<= break sample).
+// DIST: also the segment's distortion loss (k_distortion_fw's quantity for
+// these ws, zero past the termination sample) into *dist, from the chunk
+// loop's registers: with the exclusive scans W_ex, WT_ex of w and w t the
+// per-sample term 2 (WT_in W_ex - W_in WT_ex) is 2 w (t W_ex - WT_ex), a sum
+// of non-negative products; t is taken relative to the segment's first
+// sample (the loss is translation invariant), which removes the cancellation
+// of the absolute-t scans.  Every other output is the plain instantiation's.
+template <bool DIST>
 __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __restrict__ rgbs,
                               const float* __restrict__ dl, const float* __restrict__ ts,
-                              int64_t start, int n, float thr, float* __restrict__ ws) {
+                              int64_t start, int n, float thr, float* __restrict__ ws,
+                              float* __restrict__ dist = nullptr) {
     const int lane = rn_lane();
     float T = 1.0f;
     float aO = 0.f, aD = 0.f, aR = 0.f, aG = 0.f, aB = 0.f;
+    float t0 = 0.f, pw = 0.f, pwt = 0.f, aL = 0.f;
+    if (DIST && n > 0) t0 = ts[start];
     int used = n;
     bool done = false;
     for (int base = 0; base < n; base += RN_WAVE) {
@@ -46,11 +57,12 @@ __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __rest
             if (valid) ws[start + i] = 0.f;
             continue;
         }
-        float a = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, t = 0.f;
+        float a = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, t = 0.f, d = 0.f;
         if (valid) {
             const int64_t s = start + i;
             a = 1.0f - rn_exp_det(-sig[s] * dl[s]);
             c0 = rgbs[3 * s]; c1 = rgbs[3 * s + 1]; c2 = rgbs[3 * s + 2]; t = ts[s];
+            if (DIST) d = dl[s];
         }
         const float om = 1.0f - a;
         // transmittance after this sample = T * prod_{j<=i} (1-a_j)
@@ -70,7 +82,20 @@ __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __rest
             aR = fmaf(w, c0, aR); aG = fmaf(w, c1, aG); aB = fmaf(w, c2, aB);
             aD = fmaf(w, t, aD); aO += w;
         }
+        if (DIST) {
+            const float wl = live ? w : 0.f, tr = t - t0;
+            const float sw = pw + rn_wave_incl_sum(wl);
+            const float swt = pwt + rn_wave_incl_sum(wl * tr);
+            const float ex_w = rn_wave_shr1(sw, pw), ex_wt = rn_wave_shr1(swt, pwt);
+            aL += 2.0f * (wl * (tr * ex_w - ex_wt)) + (1.0f / 3) * wl * wl * d;
+            pw = rn_wave_last(sw);
+            pwt = rn_wave_last(swt);
+        }
         T = rn_wave_last(pin);
+    }
+    if (DIST) {
+        aL = rn_wave_sum(aL);
+        if (lane == 0) *dist = aL;
     }
     SegOut o;
     o.O = rn_wave_sum(aO); o.D = rn_wave_sum(aD);
@@ -80,22 +105,42 @@ __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __rest
 }
 
 // Backward over one segment (volumerendering.cu:109-151).  Seeds are per ray.
+// DIST: dL_dws is not read; it is the distortion loss's gradient
+// (losses.cu:113-142, k_distortion_bw) for the seed g on this segment's loss
+// `dist`, formed per sample in registers from the scans of w and w t carried
+// over the chunks (t relative to the first sample, as the forward) and the
+// segment totals, which one pass over ws / ts collects first in the chunk
+// loop's own scan order (so total - inclusive is exactly 0 at the last
+// sample).  The loss is homogeneous of degree 2 in ws, so the total of
+// dL_dws * ws (the thrust scan's last element) is 2 g dist.
+template <bool DIST>
 __device__ void seg_backward(const float* __restrict__ sig, const float* __restrict__ rgbs,
                              const float* __restrict__ dl, const float* __restrict__ ts,
                              const float* __restrict__ ws, const float* __restrict__ dL_dws,
                              int64_t start, int n, float thr, float R, float G, float B, float O,
                              float D, float gR, float gG, float gB, float gO, float gD,
-                             float* __restrict__ dsig, float* __restrict__ drgb) {
+                             float* __restrict__ dsig, float* __restrict__ drgb, float g = 0.f,
+                             float dist = 0.f) {
     const int lane = rn_lane();
     // total of dL_dws*ws over the whole segment (thrust scan's last element)
     float wsum_part = 0.f;
-    if (dL_dws) {
+    float t0 = 0.f, Wtot = 0.f, WTtot = 0.f, qw = 0.f, qwt = 0.f;
+    if (DIST) {
+        if (n > 0) t0 = ts[start];
+        for (int base = 0; base < n; base += RN_WAVE) {
+            const int i = base + lane;
+            float w = 0.f, t = 0.f;
+            if (i < n) { w = ws[start + i]; t = ts[start + i]; }
+            Wtot = rn_wave_last(Wtot + rn_wave_incl_sum(w));
+            WTtot = rn_wave_last(WTtot + rn_wave_incl_sum(w * (t - t0)));
+        }
+    } else if (dL_dws) {
         for (int base = 0; base < n; base += RN_WAVE) {
             const int i = base + lane;
             if (i < n) wsum_part += dL_dws[start + i] * ws[start + i];
         }
     }
-    const float wtot = dL_dws ? rn_wave_sum(wsum_part) : 0.f;
+    const float wtot = DIST ? 2.0f * g * dist : (dL_dws ? rn_wave_sum(wsum_part) : 0.f);
     const float gterm_O = gO * (1 - O);
     float T = 1.0f, pr = 0.f, pg = 0.f, pb = 0.f, pd = 0.f, pw = 0.f;
     bool done = false;
@@ -112,7 +157,7 @@ __device__ void seg_backward(const float* __restrict__ sig, const float* __restr
             d = dl[s];
             a = 1.0f - rn_exp_det(-sig[s] * d);
             c0 = rgbs[3 * s]; c1 = rgbs[3 * s + 1]; c2 = rgbs[3 * s + 2]; t = ts[s];
-            if (dL_dws) { gw = dL_dws[s]; wsv = ws[s]; }
+            if (!DIST && dL_dws) { gw = dL_dws[s]; wsv = ws[s]; }
         }
         const float om = 1.0f - a;
         const float pin = rn_wave_incl_prod(lane == 0 ? T * om : om);
@@ -122,6 +167,19 @@ __device__ void seg_backward(const float* __restrict__ sig, const float* __restr
         const bool stop = brk >= 0;
         const int last = stop ? brk : RN_WAVE - 1;
         const bool live = valid && lane <= last;
+        if (DIST) {
+            wsv = live ? w : 0.f;
+            const float tr = t - t0;
+            const float W_in = qw + rn_wave_incl_sum(wsv);
+            const float WT_in = qwt + rn_wave_incl_sum(wsv * tr);
+            const float W_ex = rn_wave_shr1(W_in, qw), WT_ex = rn_wave_shr1(WT_in, qwt);
+            const float front = tr * W_ex - WT_ex;
+            const float back = (WTtot - WT_in) - tr * (Wtot - W_in);
+            // + 0: a zero seed gives +0 like the plain kernel's absent dL_dws
+            gw = (g * 2 * (front + back) + g * (2.0f / 3) * wsv * d) + 0.0f;
+            qw = rn_wave_last(W_in);
+            qwt = rn_wave_last(WT_in);
+        }
         // inclusive prefix sums (r, g, b, d accumulate before the gradient)
         const float sr = pr + rn_wave_incl_sum(live ? w * c0 : 0.f);
         const float sg = pg + rn_wave_incl_sum(live ? w * c1 : 0.f);
@@ -162,7 +220,7 @@ k_composite_fw(int n_rows, const float* __restrict__ sig, const float* __restric
     if (row >= n_rows) return;
     const int64_t ray = rays_a[3 * row], start = rays_a[3 * row + 1];
     const int n = (int)rays_a[3 * row + 2];
-    SegOut o = seg_forward(sig, rgbs, dl, ts, start, n, thr, ws);
+    SegOut o = seg_forward<false>(sig, rgbs, dl, ts, start, n, thr, ws);
     if (rn_lane() == 0) {
         total[ray] = o.used;
         opacity[ray] = o.O; depth[ray] = o.D;
@@ -183,9 +241,10 @@ k_composite_bw(int n_rows, const float* __restrict__ gO, const float* __restrict
     if (row >= n_rows) return;
     const int64_t ray = rays_a[3 * row], start = rays_a[3 * row + 1];
     const int n = (int)rays_a[3 * row + 2];
-    seg_backward(sig, rgbs, dl, ts, ws, dL_dws, start, n, thr, rgb[3 * ray], rgb[3 * ray + 1],
-                 rgb[3 * ray + 2], opacity[ray], depth[ray], gRGB[3 * ray], gRGB[3 * ray + 1],
-                 gRGB[3 * ray + 2], gO[ray], gD[ray], dsig, drgb);
+    seg_backward<false>(sig, rgbs, dl, ts, ws, dL_dws, start, n, thr, rgb[3 * ray],
+                        rgb[3 * ray + 1], rgb[3 * ray + 2], opacity[ray], depth[ray],
+                        gRGB[3 * ray], gRGB[3 * ray + 1], gRGB[3 * ray + 2], gO[ray], gD[ray],
+                        dsig, drgb);
 }
 
 // volumerendering.cu:206-250; thread per alive ray (<= 64 samples per call)
@@ -229,7 +288,27 @@ k_ml_composite_fw(int n_rays, int K, const float* __restrict__ sig,
                   float* __restrict__ ws) {
     const int seg = blockIdx.x * (blockDim.x / RN_WAVE) + (threadIdx.x / RN_WAVE);
     if (seg >= n_rays * K) return;
-    SegOut o = seg_forward(sig, rgbs, dl, ts, offsets[seg], counts[seg], thr, ws);
+    SegOut o = seg_forward<false>(sig, rgbs, dl, ts, offsets[seg], counts[seg], thr, ws);
+    if (rn_lane() == 0) {
+        used[seg] = o.used;
+        Ok[seg] = o.O; Dk[seg] = o.D;
+        RGBk[3 * seg] = o.R; RGBk[3 * seg + 1] = o.G; RGBk[3 * seg + 2] = o.B;
+    }
+}
+
+// the same, plus the per-segment distortion loss dist_k[K][B] (rn_ml_composite_dist_fw)
+__global__ void __launch_bounds__(256)
+k_ml_composite_dist_fw(int n_rays, int K, const float* __restrict__ sig,
+                       const float* __restrict__ rgbs, const float* __restrict__ dl,
+                       const float* __restrict__ ts, const int32_t* __restrict__ counts,
+                       const int32_t* __restrict__ offsets, float thr,
+                       int32_t* __restrict__ used, float* __restrict__ Ok,
+                       float* __restrict__ Dk, float* __restrict__ RGBk, float* __restrict__ ws,
+                       float* __restrict__ dist_k) {
+    const int seg = blockIdx.x * (blockDim.x / RN_WAVE) + (threadIdx.x / RN_WAVE);
+    if (seg >= n_rays * K) return;
+    SegOut o = seg_forward<true>(sig, rgbs, dl, ts, offsets[seg], counts[seg], thr, ws,
+                                 dist_k + seg);
     if (rn_lane() == 0) {
         used[seg] = o.used;
         Ok[seg] = o.O; Dk[seg] = o.D;
@@ -300,9 +379,37 @@ k_ml_composite_bw(int n_rays, int K, const float* __restrict__ gRGB,
     const float bgdot = bg[0] * gRGB[3 * r] + bg[1] * gRGB[3 * r + 1] + bg[2] * gRGB[3 * r + 2];
     const float go = g * (gO[r] - bgdot);
     const float gd = gDepth ? gDepth[r * K + k] : 0.f;
-    seg_backward(sig, rgbs, dl, ts, nullptr, nullptr, offsets[seg], counts[seg], thr,
-                 RGBk[3 * seg], RGBk[3 * seg + 1], RGBk[3 * seg + 2], Ok[seg], Dk[seg], gr, gg,
-                 gb, go, gd, dsig, drgb);
+    seg_backward<false>(sig, rgbs, dl, ts, nullptr, nullptr, offsets[seg], counts[seg], thr,
+                        RGBk[3 * seg], RGBk[3 * seg + 1], RGBk[3 * seg + 2], Ok[seg], Dk[seg], gr,
+                        gg, gb, go, gd, dsig, drgb);
+}
+
+// the same, plus the distortion loss's seed per segment: gdist[K][B] or, when
+// that is null, the constant gdist_c (rn_ml_composite_dist_bw); reads the ws
+// and dist_k that k_ml_composite_dist_fw wrote
+__global__ void __launch_bounds__(256)
+k_ml_composite_dist_bw(int n_rays, int K, const float* __restrict__ gRGB,
+                       const float* __restrict__ gO, const float* __restrict__ gDepth,
+                       const float* __restrict__ gdist, float gdist_c,
+                       const float* __restrict__ gate, const float* __restrict__ bg,
+                       const float* __restrict__ sig, const float* __restrict__ rgbs,
+                       const float* __restrict__ dl, const float* __restrict__ ts,
+                       const float* __restrict__ ws, const int32_t* __restrict__ counts,
+                       const int32_t* __restrict__ offsets, const float* __restrict__ Ok,
+                       const float* __restrict__ Dk, const float* __restrict__ RGBk,
+                       const float* __restrict__ dist_k, float thr, float* __restrict__ dsig,
+                       float* __restrict__ drgb) {
+    const int seg = blockIdx.x * (blockDim.x / RN_WAVE) + (threadIdx.x / RN_WAVE);
+    if (seg >= n_rays * K) return;
+    const int k = seg / n_rays, r = seg - k * n_rays;
+    const float g = gate[r * K + k];
+    const float gr = g * gRGB[3 * r], gg = g * gRGB[3 * r + 1], gb = g * gRGB[3 * r + 2];
+    const float bgdot = bg[0] * gRGB[3 * r] + bg[1] * gRGB[3 * r + 1] + bg[2] * gRGB[3 * r + 2];
+    const float go = g * (gO[r] - bgdot);
+    const float gd = gDepth ? gDepth[r * K + k] : 0.f;
+    seg_backward<true>(sig, rgbs, dl, ts, ws, nullptr, offsets[seg], counts[seg], thr,
+                       RGBk[3 * seg], RGBk[3 * seg + 1], RGBk[3 * seg + 2], Ok[seg], Dk[seg], gr,
+                       gg, gb, go, gd, dsig, drgb, gdist ? gdist[seg] : gdist_c, dist_k[seg]);
 }
 
 // ---------------------------------------------------------------------------
@@ -437,6 +544,22 @@ int rn_ml_composite_fw(const float* sigmas, const float* rgbs, const float* delt
     return 0;
 }
 
+int rn_ml_composite_dist_fw(const float* sigmas, const float* rgbs, const float* deltas,
+                            const float* ts, const int32_t* counts, const int32_t* offsets,
+                            int64_t n_rays, int32_t n_models, float T_threshold, int32_t* used,
+                            float* opacity_k, float* depth_k, float* rgb_k, float* ws,
+                            float* dist_k, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_models >= 1, "bad sizes");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(counts && offsets && used && opacity_k && depth_k && rgb_k && dist_k,
+                 "null pointer");
+    k_ml_composite_dist_fw<<<nblk(n_rays * n_models, 4), 256, 0, (hipStream_t)stream>>>(
+        (int)n_rays, n_models, sigmas, rgbs, deltas, ts, counts, offsets, T_threshold, used,
+        opacity_k, depth_k, rgb_k, ws, dist_k);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
 int rn_ml_combine_fw(const float* gate, const float* opacity_k, const float* depth_k,
                      const float* rgb_k, const float* bg, int64_t n_rays, int32_t n_models,
                      float* rgb, float* opacity, float* depth, void* stream) {
@@ -476,6 +599,26 @@ int rn_ml_composite_bw(const float* dL_drgb, const float* dL_dopacity, const flo
     k_ml_composite_bw<<<nblk(n_rays * n_models, 4), 256, 0, (hipStream_t)stream>>>(
         (int)n_rays, n_models, dL_drgb, dL_dopacity, dL_ddepth, gate, bg, sigmas, rgbs, deltas,
         ts, counts, offsets, opacity_k, depth_k, rgb_k, T_threshold, dL_dsigmas, dL_drgbs);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_ml_composite_dist_bw(const float* dL_drgb, const float* dL_dopacity,
+                            const float* dL_ddepth, const float* dL_ddist, float dL_ddist_const,
+                            const float* gate, const float* bg, const float* sigmas,
+                            const float* rgbs, const float* deltas, const float* ts,
+                            const float* ws, const int32_t* counts, const int32_t* offsets,
+                            const float* opacity_k, const float* depth_k, const float* rgb_k,
+                            const float* dist_k, int64_t n_rays, int32_t n_models,
+                            float T_threshold, float* dL_dsigmas, float* dL_drgbs, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_models >= 1, "bad sizes");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(dL_drgb && dL_dopacity && gate && bg && counts && offsets && opacity_k &&
+                 depth_k && rgb_k && ws && dist_k, "null pointer");
+    k_ml_composite_dist_bw<<<nblk(n_rays * n_models, 4), 256, 0, (hipStream_t)stream>>>(
+        (int)n_rays, n_models, dL_drgb, dL_dopacity, dL_ddepth, dL_ddist, dL_ddist_const, gate, bg,
+        sigmas, rgbs, deltas, ts, ws, counts, offsets, opacity_k, depth_k, rgb_k, dist_k,
+        T_threshold, dL_dsigmas, dL_drgbs);
     RN_CHECK_LAUNCH();
     return 0;
 }

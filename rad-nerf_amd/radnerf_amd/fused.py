@@ -86,7 +86,17 @@ class Workspace:
         self.queue = torch.zeros(3, **i)
         self._bwd_scratch = None
         self._chunks = None
+        self._dist_k = None         # per-segment distortion loss (distortion steps only)
         self.generation = 0         # forwards run through this workspace (_MLRenderFn)
+
+    @property
+    def dist_k(self):
+        """[K][B] distortion loss per (sub-NeRF, ray) segment, written by
+        rn_ml_composite_dist_fw and read by its backward; allocated by the
+        first distortion step."""
+        if self._dist_k is None:
+            self._dist_k = torch.empty(self.K, self.B, device=self.device, dtype=torch.float32)
+        return self._dist_k
 
     def chunk_list(self, max_chunk, min_chunk, head_chunks=0, balance_blocks=0):
         """rn_bwd_plan's chunk list, sized for the workspace capacity."""
@@ -420,7 +430,10 @@ class FusedMLRenderer:
 
     # ------------------------------------------------------------------ forward
     def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4,
-                exp_step_factor=0.0):
+                exp_step_factor=0.0, distortion=False):
+        """distortion: the composite also writes each segment's Mip-NeRF 360
+        distortion loss into ws.dist_k (rn_ml_composite_dist_fw; every other
+        output is the plain kernel's), for backward(dL_ddist=...)."""
         m, g, w, L = self.model, self.gate, self.ws, lib()
         B, K, G = rays_o.shape[0], m.size, g.out_dim     # K rendered here, G gated
         assert B == w.B and noise.shape == (K, B)
@@ -460,10 +473,15 @@ class FusedMLRenderer:
             # the plan also writes the level forward's per-position input
             self._plan(st, rays_o, rays_d if self.level_fwd and self.plan_prep else None)
         self._field(True, rays_o, rays_d, st)
-        self._ev("composite_fw", L.ml_composite_fw, w.sigma.data_ptr(), w.rgb.data_ptr(), w.deltas.data_ptr(),
-                          w.ts.data_ptr(), w.counts.data_ptr(), w.offsets.data_ptr(), B, K,
-                          float(T_threshold), w.used.data_ptr(), w.opacity_k.data_ptr(),
-                          w.depth_k.data_ptr(), w.rgb_k.data_ptr(), w.ws.data_ptr(), st)
+        comp = (w.sigma.data_ptr(), w.rgb.data_ptr(), w.deltas.data_ptr(),
+                w.ts.data_ptr(), w.counts.data_ptr(), w.offsets.data_ptr(), B, K,
+                float(T_threshold), w.used.data_ptr(), w.opacity_k.data_ptr(),
+                w.depth_k.data_ptr(), w.rgb_k.data_ptr(), w.ws.data_ptr())
+        self._dist_forward = bool(distortion)       # dist_k holds this step's losses
+        if distortion:
+            self._ev("composite_dist_fw", L.ml_composite_dist_fw, *comp, w.dist_k.data_ptr(), st)
+        else:
+            self._ev("composite_fw", L.ml_composite_fw, *comp, st)
         # per-ray outputs of all G gated sub-NeRFs (here: the K rendered ones;
         # pinned.PinnedMLRenderer gathers them from every rank)
         ok, dk, rk = self._gather_model_outputs()
@@ -729,9 +747,12 @@ class FusedMLRenderer:
     # ----------------------------------------------------------------- backward
     def backward(self, rays_o, rays_d, gate_in2, gate, bg, dL_drgb, dL_dopacity, dL_ddepth,
                  dL_dgate_ext=None, T_threshold=1e-4, grid_grad=None, mlp_grad=None,
-                 gate_grad=None):
+                 gate_grad=None, dL_ddist=None):
         """Accumulates into grid_grad / mlp_grad / gate_grad (zero-initialised
-        by the caller or allocated here) and returns them."""
+        by the caller or allocated here) and returns them.  dL_ddist: the seed
+        on the per-segment distortion loss of a forward(distortion=True) --
+        a [K][B] fp32 tensor, or a number for the same seed on every segment;
+        None runs the plain composite backward."""
         m, g, w, L = self.model, self.gate, self.ws, lib()
         B, K, G = rays_o.shape[0], m.size, g.out_dim
         dev = rays_o.device
@@ -773,13 +794,30 @@ class FusedMLRenderer:
             gate_bwd(side)
         gate_k = self._local_cols(gate)
         ddepth_k = None if dL_ddepth is None else self._local_cols(dL_ddepth)
-        self._ev("composite_bw", L.ml_composite_bw, dL_drgb.data_ptr(), dL_dopacity.data_ptr(),
-                          None if ddepth_k is None else ddepth_k.data_ptr(), gate_k.data_ptr(),
-                          bg.data_ptr(), w.sigma.data_ptr(), w.rgb.data_ptr(),
-                          w.deltas.data_ptr(), w.ts.data_ptr(), w.counts.data_ptr(),
-                          w.offsets.data_ptr(), w.opacity_k.data_ptr(), w.depth_k.data_ptr(),
-                          w.rgb_k.data_ptr(), B, K, float(T_threshold), w.dsigma.data_ptr(),
-                          w.drgb.data_ptr(), st)
+        if dL_ddist is None:
+            self._ev("composite_bw", L.ml_composite_bw, dL_drgb.data_ptr(), dL_dopacity.data_ptr(),
+                     None if ddepth_k is None else ddepth_k.data_ptr(), gate_k.data_ptr(),
+                     bg.data_ptr(), w.sigma.data_ptr(), w.rgb.data_ptr(),
+                     w.deltas.data_ptr(), w.ts.data_ptr(), w.counts.data_ptr(),
+                     w.offsets.data_ptr(), w.opacity_k.data_ptr(), w.depth_k.data_ptr(),
+                     w.rgb_k.data_ptr(), B, K, float(T_threshold), w.dsigma.data_ptr(),
+                     w.drgb.data_ptr(), st)
+        else:
+            if not getattr(self, "_dist_forward", False):
+                raise RuntimeError("backward(dL_ddist=...): the forward of this step ran "
+                                   "without distortion=True")
+            seed = torch.is_tensor(dL_ddist)
+            if seed:
+                assert dL_ddist.shape == (K, B) and dL_ddist.dtype == torch.float32 \
+                    and dL_ddist.is_contiguous()
+            self._ev("composite_dist_bw", L.ml_composite_dist_bw, dL_drgb.data_ptr(),
+                     dL_dopacity.data_ptr(), None if ddepth_k is None else ddepth_k.data_ptr(),
+                     dL_ddist.data_ptr() if seed else None, 0.0 if seed else float(dL_ddist),
+                     gate_k.data_ptr(), bg.data_ptr(), w.sigma.data_ptr(), w.rgb.data_ptr(),
+                     w.deltas.data_ptr(), w.ts.data_ptr(), w.ws.data_ptr(), w.counts.data_ptr(),
+                     w.offsets.data_ptr(), w.opacity_k.data_ptr(), w.depth_k.data_ptr(),
+                     w.rgb_k.data_ptr(), w.dist_k.data_ptr(), B, K, float(T_threshold),
+                     w.dsigma.data_ptr(), w.drgb.data_ptr(), st)
         if gate_at == "field":          # side stream, beside field_bwd
             gate_bwd(side)
         elif gate_at == "main":         # in line, before field_bwd
@@ -831,28 +869,34 @@ class FusedMLRenderer:
     # --------------------------------------------------------------- train step
     def train_step(self, rays_o, rays_d, gate_in2, target_rgb, noise, bg, lambda_opacity=1e-3,
                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0, T_threshold=1e-4,
-                   exp_step_factor=0.0, grid_grad=None, mlp_grad=None, gate_grad=None):
+                   exp_step_factor=0.0, grid_grad=None, mlp_grad=None, gate_grad=None,
+                   lambda_distortion=0.0):
         """render -> NeRFLoss -> backward of train_ml.py:179-192 as one launch
         chain: the fused loss kernel writes the backward seeds directly.
         Returns ({term: mean}, (grid_grad, mlp_grad, gate_grad)); gradients are
-        accumulated into the given buffers (zero them first)."""
+        accumulated into the given buffers (zero them first).
+        lambda_distortion > 0 adds NeRFLoss's distortion term (losses.py:63-67:
+        lambda * sum over sub-NeRFs of the per-ray loss's mean) inside the
+        composite kernels: the seed is the constant lambda / B per segment."""
         from .losses import fused_nerf_loss
+        dist = lambda_distortion > 0
         rgb, opacity, depth, gate, imp = self.forward(rays_o, rays_d, gate_in2, noise, bg,
-                                                      T_threshold, exp_step_factor)
+                                                      T_threshold, exp_step_factor, dist)
         terms, (d_rgb, d_op, d_depth, d_gate) = fused_nerf_loss(
             rgb, target_rgb, opacity, depth, gate, imp, lambda_opacity, lambda_cv_importance,
-            lambda_depth_mutual)
+            lambda_depth_mutual, lambda_distortion, self.ws.dist_k if dist else None)
         grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth, d_gate,
-                              T_threshold, grid_grad, mlp_grad, gate_grad)
+                              T_threshold, grid_grad, mlp_grad, gate_grad,
+                              float(lambda_distortion) / rays_o.shape[0] if dist else None)
         return terms, grads
 
 
 class _MLRenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid_params, mlp_params, gate_params, renderer, rays_o, rays_d, gate_in2,
-                noise, bg, T_threshold, esf):
+                noise, bg, T_threshold, esf, distortion=False):
         rgb, opacity, depth, gate, imp = renderer.forward(rays_o, rays_d, gate_in2, noise, bg,
-                                                          T_threshold, esf)
+                                                          T_threshold, esf, distortion)
         # the backward reads this step's samples from the renderer's workspace:
         # stamp it, so a second forward through the same workspace before this
         # backward is caught instead of silently differentiating the wrong step
@@ -861,10 +905,13 @@ class _MLRenderFn(torch.autograd.Function):
         ctx.renderer = renderer
         ctx.save_for_backward(rays_o, rays_d, gate_in2, gate, bg)
         ctx.T = T_threshold
+        if distortion:
+            # fifth output: the per-ray distortion loss of every sub-NeRF, (B, K)
+            return rgb, opacity, depth, gate, renderer.ws.dist_k.t().contiguous()
         return rgb, opacity, depth, gate
 
     @staticmethod
-    def backward(ctx, d_rgb, d_op, d_depth, d_gate):
+    def backward(ctx, d_rgb, d_op, d_depth, d_gate, d_dist=None):
         rays_o, rays_d, gate_in2, gate, bg = ctx.saved_tensors
         if ctx.renderer.ws.generation != ctx.generation:
             raise RuntimeError(
@@ -878,12 +925,14 @@ class _MLRenderFn(torch.autograd.Function):
         d_op = z(B) if d_op is None else d_op.float().contiguous()
         d_depth = None if d_depth is None else d_depth.float().contiguous()
         d_gate = None if d_gate is None else d_gate.float().contiguous()
+        # the kernel's seed layout is [K][B]
+        d_dist = None if d_dist is None else d_dist.float().t().contiguous()
         r = ctx.renderer
         need_o, need_d, need_2 = ctx.needs_input_grad[4:7]
         r.input_grad = bool(need_o or need_d or need_2)
         try:
             gg, mg, ag = r.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
-                                    d_gate, ctx.T)
+                                    d_gate, ctx.T, dL_ddist=d_dist)
         finally:
             input_grad, r.input_grad = r.input_grad, False
         do = dd = d2 = None
@@ -892,7 +941,7 @@ class _MLRenderFn(torch.autograd.Function):
             do = w.drays_o + w.gate_dx[:, 0:3] if need_o else None
             dd = w.drays_d.clone() if need_d else None
             d2 = w.gate_dx[:, 3:6].contiguous() if need_2 else None
-        return gg, mg, ag, None, do, dd, d2, None, None, None, None
+        return gg, mg, ag, None, do, dd, d2, None, None, None, None, None
 
 
 class _GradNotSupported(torch.autograd.Function):
@@ -960,7 +1009,12 @@ def release_renderers():
 
 
 def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **kwargs):
-    """Same result dict as ml_rendering.ml_render (train mode)."""
+    """Same result dict as ml_rendering.ml_render (train mode).
+    distortion=True adds "distortion": fp32 (B, K), column i the per-ray
+    Mip-NeRF 360 distortion loss of sub-NeRF i (DistortionLoss.apply on its
+    ws / deltas / ts / rays_a; not gate-weighted, losses.py:63-67), computed
+    and differentiated inside the composite kernels.  NeRFLoss(lambda_distortion
+    > 0) reads it."""
     rays_o, rays_d = rays_o.float().contiguous(), rays_d.float().contiguous()
     second = imgs_d.float().contiguous() if gating_net.type == "image" else rays_d
     B, K, dev = rays_o.shape[0], model.size, rays_o.device
@@ -975,9 +1029,13 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     else:
         bg = torch.zeros(3, device=dev)
     r = get_renderer(model, gating_net, B, grad=torch.is_grad_enabled())
-    rgb, opacity, depth, gate = _MLRenderFn.apply(
-        model.xyz_encoder.params, model.mlp_params, gating_net.params, r, rays_o, rays_d, second,
-        noise.contiguous(), bg, float(kwargs.get("T_threshold", 1e-4)), esf)
+    distortion = bool(kwargs.get("distortion", False))
+    fn_args = (model.xyz_encoder.params, model.mlp_params, gating_net.params, r, rays_o, rays_d,
+               second, noise.contiguous(), bg, float(kwargs.get("T_threshold", 1e-4)), esf)
+    if distortion:
+        rgb, opacity, depth, gate, dist = _MLRenderFn.apply(*fn_args, True)
+    else:
+        rgb, opacity, depth, gate = _MLRenderFn.apply(*fn_args)
     w = r.ws
     # each sub-NeRF's own colour (ml_rendering.py:65,73): values only -- a loss
     # on them raises at backward (the fused backward seeds the combined rgb)
@@ -985,5 +1043,8 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     singles = [grad_unsupported(w.rgb_k[i] + bg * (1 - w.opacity_k[i])[:, None],
                                 anchors, "ml_render independent_rgbs")
                for i in range(K)]
-    return {"rgb": rgb, "independent_rgbs": singles, "depth": depth, "opacity": opacity,
-            "gating_code": gate, "gating_importance": gate.sum(0)}
+    out = {"rgb": rgb, "independent_rgbs": singles, "depth": depth, "opacity": opacity,
+           "gating_code": gate, "gating_importance": gate.sum(0)}
+    if distortion:
+        out["distortion"] = dist
+    return out

@@ -54,7 +54,14 @@ class NeRFLoss(nn.Module):
         if lambda_disp > 0:
             loss["disp"] = lambda_disp * results["disp"] ** 2
         K = results["gating_code"].shape[-1]
-        if lambda_distortion > 0:
+        if lambda_distortion > 0 and "distortion" in results:
+            # the render's own per-ray loss of every sub-NeRF, (B, K) (or (B,)
+            # from render()): ml_render(..., distortion=True) on either chain
+            dist = results["distortion"]
+            dist = dist[:, None] if dist.dim() == 1 else dist
+            loss["distortion"] = lambda_distortion * sum(
+                dist[:, i].mean() for i in range(dist.shape[1]))
+        elif lambda_distortion > 0:
             # per sub-NeRF keys ws_i / deltas_i / ts_i / rays_a_i (losses.py:63-67)
             loss["distortion"] = 0
             for i in range(K):
@@ -72,9 +79,14 @@ class NeRFLoss(nn.Module):
 
 
 def fused_nerf_loss(rgb, target_rgb, opacity, depth, gate, importance, lambda_opacity=1e-3,
-                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0):
+                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0, lambda_distortion=0.0,
+                    dist_k=None):
     """Returns ({term: mean (0-d tensor)}, (dL_drgb, dL_dopacity, dL_ddepth, dL_dgate))
-    for loss = sum of the term means.  All inputs fp32 CUDA, contiguous."""
+    for loss = sum of the term means.  All inputs fp32 CUDA, contiguous.
+    lambda_distortion > 0 with dist_k (the [K][B] per-segment distortion loss
+    of FusedMLRenderer.forward(distortion=True)) reports terms["distortion"] =
+    lambda * sum_k mean_rays; its seed, the constant lambda / B per segment,
+    goes to FusedMLRenderer.backward(dL_ddist=...)."""
     B, K = gate.shape
     dev = rgb.device
     f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
@@ -89,6 +101,8 @@ def fused_nerf_loss(rgb, target_rgb, opacity, depth, gate, importance, lambda_op
                     d_rgb.data_ptr(), d_op.data_ptr(), d_depth.data_ptr(), d_gate.data_ptr(),
                     torch.cuda.current_stream(dev).cuda_stream)
     terms = {"rgb": out[0] / (3 * B), "opacity": out[1] / B}
+    if lambda_distortion > 0 and dist_k is not None:
+        terms["distortion"] = lambda_distortion * dist_k.sum() / B
     if lambda_cv_importance > 0 and K > 1:
         terms["cv_importance"] = out[2]
     if lambda_depth_mutual > 0 and K > 1:

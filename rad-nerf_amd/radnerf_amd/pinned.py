@@ -97,7 +97,13 @@ class PinnedMLRenderer(FusedMLRenderer):
         self.rgb_all = torch.empty(K, B, 3, **f)
         self._dgate_all = torch.empty(B, K, **f)
 
-    def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4, exp_step_factor=0.0):
+    _NO_DISTORTION = ("PinnedMLRenderer: the in-chain distortion loss is not supported in the "
+                      "sub-NeRF-per-GPU layout; use the data-parallel renderer")
+
+    def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4, exp_step_factor=0.0,
+                distortion=False):
+        if distortion:
+            raise NotImplementedError(self._NO_DISTORTION)
         return super().forward(rays_o, rays_d, gate_in2, noise[self.k0:self.k1], bg, T_threshold,
                                exp_step_factor)
 
@@ -136,8 +142,10 @@ class PinnedMLRenderer(FusedMLRenderer):
 
     def backward(self, rays_o, rays_d, gate_in2, gate, bg, dL_drgb, dL_dopacity, dL_ddepth,
                  dL_dgate_ext=None, T_threshold=1e-4, grid_grad=None, mlp_grad=None,
-                 gate_grad=None):
+                 gate_grad=None, dL_ddist=None):
         """mlp_grad: the full (K, FIELD_PARAMS) buffer; this rank adds its rows."""
+        if dL_ddist is not None:
+            raise NotImplementedError(self._NO_DISTORTION)
         if self.input_grad:
             # each rank would hold the ray gradients of its own sub-NeRFs only
             raise NotImplementedError(

@@ -25,6 +25,7 @@ from . import vren
 from ._lib import lib
 from .custom_functions import RayAABBIntersector, RayMarcher, VolumeRenderer
 from .fused import grad_unsupported
+from .losses import DistortionLoss
 
 MAX_SAMPLES = 1024
 NEAR_DISTANCE = 0.01
@@ -62,6 +63,10 @@ def _train_rays(model, rays_o, rays_d, hits_t, bitfield, call_model, kw):
     bg = _background(esf, kw.get("random_bg", False), rays_o.device)
     out.update({"vr_samples": vr, "opacity": opacity, "depth": depth, "ws": ws,
                 "rays_a": rays_a, "rgb": rgb + bg * (1 - opacity)[:, None]})
+    if kw.get("distortion", False):
+        # per-ray distortion loss (losses.py:6-36), differentiable through
+        # VolumeRenderer's dL_dws
+        out["distortion"] = DistortionLoss.apply(ws, deltas, ts, rays_a)
     return out
 
 
@@ -166,7 +171,9 @@ class _TrainResults(dict):
     the sample count), so a training step that only reads rgb / opacity pays
     nothing for them.  Reading them after another forward has reused the
     workspace raises.  ws carries no gradient through the fused chain: a
-    loss on it (e.g. a distortion loss) raises at backward."""
+    loss on it raises at backward.  The distortion loss trains on the fused
+    chain through render(..., distortion=True)'s own "distortion" key (the
+    per-ray loss, computed and differentiated inside the composite kernels)."""
     LAZY = ("rays_a", "ws", "deltas", "ts", "rm_samples", "vr_samples")
 
     def __init__(self, base, renderer, anchor):
@@ -243,15 +250,18 @@ def _train_fused(model, rays_o, rays_d, kw):
         kw["noise"] = noise.reshape(1, -1)
     res = ml_render_fused(model, gate, rays_o, rays_d, rays_d, **kw)
     r = get_renderer(model, gate, rays_o.shape[0], grad=torch.is_grad_enabled())
-    return _TrainResults({"rgb": res["rgb"], "opacity": res["opacity"],
-                          "depth": res["depth"][:, 0]}, r,
-                         (model.mlp_params, model.xyz_encoder.params))
+    base = {"rgb": res["rgb"], "opacity": res["opacity"], "depth": res["depth"][:, 0]}
+    if "distortion" in res:
+        base["distortion"] = res["distortion"][:, 0]
+    return _TrainResults(base, r, (model.mlp_params, model.xyz_encoder.params))
 
 
 def render(model, rays_o, rays_d, **kwargs):
     """rendering.py:12-46 for a single NGP model.  Training renders take the
     fused chain (fused=True, the default); fused=False keeps the reference's
-    op-by-op autograd structure (RayMarcher -> model -> VolumeRenderer)."""
+    op-by-op autograd structure (RayMarcher -> model -> VolumeRenderer).
+    distortion=True (training renders) adds "distortion": the per-ray
+    Mip-NeRF 360 distortion loss (B,), differentiable on both chains."""
     fused = kwargs.pop("fused", True)
     if fused and not kwargs.get("test_time", False):
         return _to_host(_train_fused(model, rays_o, rays_d, kwargs), kwargs)
@@ -279,7 +289,13 @@ def _to_host(res, kw):
 
 def ml_render(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **kwargs):
     """ml_rendering.py:11-78: gate, K sub-NeRF renders, gate-weighted combine.
-    fused (default: training renders) routes to radnerf_amd.fused."""
+    fused (default: training renders) routes to radnerf_amd.fused.
+    distortion=True (training renders) adds "distortion", fp32 (B, K): column
+    i is DistortionLoss of sub-NeRF i's samples (not gate-weighted).  On the
+    fused chain the composite kernels compute and differentiate it; with
+    fused=False it is DistortionLoss.apply on the reference's per-sub-NeRF keys
+    ws_i / deltas_i / ts_i / rays_a_i (losses.py:63-67), which are returned
+    too.  NeRFLoss(lambda_distortion > 0) works on either result."""
     fused = kwargs.pop("fused", True)
     if fused and not kwargs.get("test_time", False):
         from .fused import ml_render_fused
@@ -292,7 +308,8 @@ def ml_render(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **kwargs)
         rgb_acc = torch.zeros(B, 3, device=dev)
         op_acc = torch.zeros(B, device=dev)
         depth_all = torch.zeros(B, K, device=dev)
-        singles, total_k = [], []
+        singles, total_k, dist_k, per_model = [], [], [], {}
+        distortion = kwargs.get("distortion", False) and not kwargs.get("test_time", False)
         noise = kwargs.pop("noise", None)
         fn = _test_rays if kwargs.get("test_time", False) else _train_rays
         test_fused = None
@@ -313,6 +330,10 @@ def ml_render(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **kwargs)
                 r = fn(model, rays_o, rays_d, hits_t, getattr(model, f"density_bitfield_{i}"),
                        call, kw)
                 r = _to_host(r, kwargs)
+            if distortion:
+                for key in ("ws", "deltas", "ts", "rays_a"):
+                    per_model[f"{key}_{i}"] = r[key]
+                dist_k.append(r["distortion"])
             singles.append(r["rgb"])
             total_k.append(r["total_samples"] if "total_samples" in r else 0)
             rgb_acc = rgb_acc + r["rgb"] * gate[:, i][:, None]
@@ -323,4 +344,7 @@ def ml_render(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **kwargs)
         if kwargs.get("test_time", False):
             # samples composited over all sub-NeRFs (a device scalar)
             out["total_samples"] = sum(total_k)
+        if distortion:
+            out.update(per_model)
+            out["distortion"] = torch.stack(dist_k, 1)
         return out

@@ -26,7 +26,7 @@ class Trainer:
     def __init__(self, model, gating_net, n_rays, lr=1e-2, lambda_opacity=1e-3,
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
-                 bucketed=True):
+                 bucketed=True, lambda_distortion=0.0):
         self.model, self.gate = model, gating_net
         self.device = model.mlp_params.device
         self.renderer = FusedMLRenderer(model, gating_net, n_rays)
@@ -36,7 +36,8 @@ class Trainer:
         self.random_bg = random_bg
         self.lambdas = dict(lambda_opacity=lambda_opacity,
                             lambda_cv_importance=lambda_cv_importance,
-                            lambda_depth_mutual=lambda_depth_mutual)
+                            lambda_depth_mutual=lambda_depth_mutual,
+                            lambda_distortion=lambda_distortion)
         params = [model.xyz_encoder.params, model.mlp_params, gating_net.params]
         # gradients live in one flat buffer: one collective per step
         self.grads = rdist.GradAllReduce(params, self.device)
