@@ -574,6 +574,33 @@ int rn_get_rays(const float* directions, const float* poses, const int64_t* img_
                 const int64_t* pix_idxs, int64_t n_rays, const float* mean_dir, float* rays_o,
                 float* rays_d, float* imgs_d, void* stream);
 
+/* ---- camera pose refinement (--optimize_ext) --------------------------------
+ * rn_get_rays_pose: train_ml.py:90-96 + ray_utils.py:73-100 (axisangle_to_R)
+ * + ray_utils.py:45-70 for a batch of picks.  Per pick of image n the pose
+ * [R0 | T0] = poses[n] is refined by dR[n] (axis-angle) and dT[n], both
+ * (I,3): R = A(dR[n]) R0 with A(v) = I + (sin t / t) K + ((1 - cos t) / t^2)
+ * K^2, K = skew(v), t = |v| + 1e-7, and T = T0 + dT[n] (the rotation is not
+ * applied to the translation).  rays_d = R dir, rays_o = T, imgs_d = R
+ * mean_dir.  dR and dT may each be NULL (zero): with both zero the outputs are
+ * rn_get_rays'.  img_idxs (n) is required; pix_idxs (n) or NULL (directions
+ * are per ray); imgs_d and mean_dir may be NULL together.
+ * rn_get_rays_pose_bw: the backward the reference leaves to autograd (the
+ * dR / dT parameters of train_ml.py:129-134).  From dL/drays_o, dL/drays_d
+ * (n,3) and dL/dimgs_d ((n,3), or NULL together with mean_dir) it writes
+ * dL/ddR and dL/ddT, (n_images,3) each: every row is written (zeros for an
+ * image without a pick; nothing is accumulated, so no memset is needed), and
+ * the sums run in a fixed order without atomics: two calls give the same
+ * bits.  dR NULL: the gradient at dR = 0.  n_rays == 0 zeroes the outputs.  */
+int rn_get_rays_pose(const float* directions, const float* poses, const float* dR,
+                     const float* dT, const int64_t* img_idxs, const int64_t* pix_idxs,
+                     int64_t n_rays, const float* mean_dir, float* rays_o, float* rays_d,
+                     float* imgs_d, void* stream);
+int rn_get_rays_pose_bw(const float* directions, const float* poses, const float* dR,
+                        const int64_t* img_idxs, const int64_t* pix_idxs, int64_t n_rays,
+                        int64_t n_images, const float* mean_dir, const float* dL_drays_o,
+                        const float* dL_drays_d, const float* dL_dimgs_d, float* dL_ddR,
+                        float* dL_ddT, void* stream);
+
 /* ---- parameter packing (f32 master -> f16 MFMA fragments / f16 grid) ------*/
 int rn_pack_f16(const float* src, int64_t src_stride, const int32_t* index, int64_t n,
                 int32_t n_models, int64_t dst_stride, void* dst, void* stream);

@@ -145,6 +145,185 @@ k_get_rays(int64_t n, const float* __restrict__ dirs, const float* __restrict__ 
     }
 }
 
+// ---- pose refinement (--optimize_ext: train_ml.py:90-93, ray_utils.py:73-100)
+// Rodrigues coefficients of A(v) = I + a K + b K^2 at theta = |v| + 1e-7 and
+// their derivatives in theta.  fp32: below theta = 1e-2 the closed forms cancel
+// (theta cos - sin ~ theta^3 / 3 out of terms of size theta), so the Taylor
+// series take over there (next terms theta^4 / 120 and smaller); above it
+// 1 - cos is formed as 2 sin^2(theta / 2), which does not cancel.
+struct RodCoef { float a, b, da, db; };
+
+__device__ inline RodCoef rod_coef(float th) {
+    RodCoef c;
+    const float t2 = th * th;
+    if (th < 1e-2f) {
+        c.a = 1.0f - t2 / 6.0f;
+        c.b = 0.5f - t2 / 24.0f;
+        c.da = -th / 3.0f + th * t2 / 30.0f;
+        c.db = -th / 12.0f + th * t2 / 180.0f;
+    } else {
+        const float s = sinf(th), co = cosf(th), sh = sinf(0.5f * th);
+        const float omc = 2.0f * sh * sh;                  // 1 - cos(theta)
+        c.a = s / th;
+        c.b = omc / t2;
+        c.da = (th * co - s) / t2;
+        c.db = (th * s - 2.0f * omc) / (t2 * th);
+    }
+    return c;
+}
+
+// K = skew(v), row-major 3x3
+__device__ inline void skew3(const float* v, float* K) {
+    K[0] = 0.f;   K[1] = -v[2]; K[2] = v[1];
+    K[3] = v[2];  K[4] = 0.f;   K[5] = -v[0];
+    K[6] = -v[1]; K[7] = v[0];  K[8] = 0.f;
+}
+
+__device__ inline void mm3(const float* X, const float* Y, float* Z) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            Z[3 * i + j] = X[3 * i] * Y[j] + X[3 * i + 1] * Y[3 + j] + X[3 * i + 2] * Y[6 + j];
+}
+
+__device__ inline float dot9(const float* X, const float* Y) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s += X[i] * Y[i];
+    return s;
+}
+
+// k_get_rays with the per-image refinement applied first: R = A(dR[n]) R0,
+// T = T0 + dT[n] (the rotation is not applied to the translation, as in the
+// reference).  R is then applied with k_get_rays' dot products, so zero dR /
+// dT (A = I exactly) reproduce its outputs.
+__global__ void __launch_bounds__(256)
+k_get_rays_pose(int64_t n, const float* __restrict__ dirs, const float* __restrict__ poses,
+                const float* __restrict__ dR, const float* __restrict__ dT,
+                const int64_t* __restrict__ img_idx, const int64_t* __restrict__ pix_idx,
+                const float* __restrict__ mean_dir, float* __restrict__ rays_o,
+                float* __restrict__ rays_d, float* __restrict__ imgs_d) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int64_t im = img_idx[r];
+    const float* P = poses + 12 * im;                             // (3, 4) row-major
+    const float* d = dirs + 3 * (pix_idx ? pix_idx[r] : r);
+    float R[9];
+    if (dR) {
+        const float v[3] = {dR[3 * im], dR[3 * im + 1], dR[3 * im + 2]};
+        const float th = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) + 1e-7f;
+        const RodCoef c = rod_coef(th);
+        float K[9], K2[9], A[9], R0[9];
+        skew3(v, K);
+        mm3(K, K, K2);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            A[i] = ((i % 4 == 0) ? 1.0f : 0.0f) + (c.a * K[i] + c.b * K2[i]);
+            R0[i] = P[4 * (i / 3) + i % 3];
+        }
+        mm3(A, R0, R);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = P[4 * (i / 3) + i % 3];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        rays_d[3 * r + i] = d[0] * R[3 * i] + d[1] * R[3 * i + 1] + d[2] * R[3 * i + 2];
+        const float T0 = P[4 * i + 3];
+        rays_o[3 * r + i] = dT ? T0 + dT[3 * im + i] : T0;
+        if (imgs_d)
+            imgs_d[3 * r + i] = mean_dir[0] * R[3 * i] + mean_dir[1] * R[3 * i + 1] +
+                                mean_dir[2] * R[3 * i + 2];
+    }
+}
+
+// Backward of k_get_rays_pose into dL/ddR, dL/ddT: one 256-thread block per
+// image.  The block scans the batch's image indices (B int64 from L2 per
+// image, no sort), each thread sums its matching rays in ascending ray order,
+// then a fixed xor-butterfly per wave and a fixed-order sum over the four
+// waves: no atomics, bit-identical from run to run.  Every image's rows are
+// written (zeros when the batch holds none of its rays).
+//   dL/dT = sum g_o ;  G = sum g_d (x) d_c + (sum g_i) (x) mean_dir ;
+//   M = dL/dA = G R0^T ;
+//   dL/dv_k = a <M, E_k> + b <M, E_k K + K E_k>
+//             + (a' <M, K> + b' <M, K^2>) v_k / |v|        (0 at |v| = 0)
+constexpr int RN_POSE_ACC = 15;     // g_o (3), g_d (x) d_c (9), g_i (3)
+
+__global__ void __launch_bounds__(256)
+k_get_rays_pose_bw(int64_t n, const float* __restrict__ dirs, const float* __restrict__ poses,
+                   const float* __restrict__ dR, const int64_t* __restrict__ img_idx,
+                   const int64_t* __restrict__ pix_idx, const float* __restrict__ mean_dir,
+                   const float* __restrict__ g_o, const float* __restrict__ g_d,
+                   const float* __restrict__ g_i, float* __restrict__ d_dR,
+                   float* __restrict__ d_dT) {
+    __shared__ float red[256 / RN_WAVE][RN_POSE_ACC];
+    const int64_t im = blockIdx.x;
+    float acc[RN_POSE_ACC];
+#pragma unroll
+    for (int q = 0; q < RN_POSE_ACC; ++q) acc[q] = 0.f;
+#pragma unroll 4
+    for (int64_t r = threadIdx.x; r < n; r += 256) {
+        if (img_idx[r] != im) continue;
+        const float* d = dirs + 3 * (pix_idx ? pix_idx[r] : r);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            acc[i] += g_o[3 * r + i];
+            const float gd = g_d[3 * r + i];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[3 + 3 * i + j] += gd * d[j];
+            if (g_i) acc[12 + i] += g_i[3 * r + i];
+        }
+    }
+    const int lane = rn_lane(), wid = threadIdx.x / RN_WAVE;
+#pragma unroll
+    for (int q = 0; q < RN_POSE_ACC; ++q) {
+        float x = acc[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+        if (lane == 0) red[wid][q] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float s[RN_POSE_ACC];
+#pragma unroll
+    for (int q = 0; q < RN_POSE_ACC; ++q) {
+        float x = red[0][q];
+        for (int w = 1; w < 256 / RN_WAVE; ++w) x += red[w][q];
+        s[q] = x;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d_dT[3 * im + i] = s[i];
+    const float* P = poses + 12 * im;
+    float G[9], R0t[9], M[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            G[3 * i + j] = g_i ? s[3 + 3 * i + j] + s[12 + i] * mean_dir[j] : s[3 + 3 * i + j];
+            R0t[3 * i + j] = P[4 * j + i];
+        }
+    mm3(G, R0t, M);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (dR) { v[0] = dR[3 * im]; v[1] = dR[3 * im + 1]; v[2] = dR[3 * im + 2]; }
+    const float nv = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    const RodCoef c = rod_coef(nv + 1e-7f);
+    float K[9], K2[9];
+    skew3(v, K);
+    mm3(K, K, K2);
+    // the theta path: d theta / d v_k = v_k / |v|, torch's subgradient 0 at 0
+    const float radial = nv > 0.f ? (c.da * dot9(M, K) + c.db * dot9(M, K2)) / nv : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float e[3] = {0.f, 0.f, 0.f}, E[9], EK[9], KE[9];
+        e[k] = 1.f;
+        skew3(e, E);                                               // E_k = dK / dv_k
+        mm3(E, K, EK);
+        mm3(K, E, KE);
+        d_dR[3 * im + k] = c.a * dot9(M, E) + c.b * (dot9(M, EK) + dot9(M, KE)) + radial * v[k];
+    }
+}
+
 inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
 
 }  // namespace
@@ -199,6 +378,48 @@ int rn_get_rays(const float* directions, const float* poses, const int64_t* img_
     RN_CHECK_ARG(directions && poses && rays_o && rays_d && (!imgs_d || mean_dir), "null pointer");
     k_get_rays<<<nblk(n_rays, 256), 256, 0, (hipStream_t)stream>>>(
         n_rays, directions, poses, img_idxs, pix_idxs, mean_dir, rays_o, rays_d, imgs_d);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_get_rays_pose(const float* directions, const float* poses, const float* dR,
+                     const float* dT, const int64_t* img_idxs, const int64_t* pix_idxs,
+                     int64_t n_rays, const float* mean_dir, float* rays_o, float* rays_d,
+                     float* imgs_d, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0, "bad sizes");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(directions && poses && img_idxs && rays_o && rays_d && (!imgs_d || mean_dir),
+                 "null pointer");
+    k_get_rays_pose<<<nblk(n_rays, 256), 256, 0, (hipStream_t)stream>>>(
+        n_rays, directions, poses, dR, dT, img_idxs, pix_idxs, mean_dir, rays_o, rays_d, imgs_d);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_get_rays_pose_bw(const float* directions, const float* poses, const float* dR,
+                        const int64_t* img_idxs, const int64_t* pix_idxs, int64_t n_rays,
+                        int64_t n_images, const float* mean_dir, const float* dL_drays_o,
+                        const float* dL_drays_d, const float* dL_dimgs_d, float* dL_ddR,
+                        float* dL_ddT, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_images >= 0 && n_images <= 0x7fffffff, "bad sizes");
+    RN_CHECK_ARG(n_images == 0 || (dL_ddR && dL_ddT), "null pointer");
+    if (n_images == 0) return 0;
+    if (n_rays == 0) {
+        // no ray: every row is zero, and no kernel is needed to say so
+        if (hipMemsetAsync(dL_ddR, 0, 3 * n_images * sizeof(float), (hipStream_t)stream) !=
+                hipSuccess ||
+            hipMemsetAsync(dL_ddT, 0, 3 * n_images * sizeof(float), (hipStream_t)stream) !=
+                hipSuccess) {
+            rn_set_error("rn_get_rays_pose_bw: hipMemsetAsync failed");
+            return 2;
+        }
+        return 0;
+    }
+    RN_CHECK_ARG(directions && poses && img_idxs && dL_drays_o && dL_drays_d &&
+                 (!dL_dimgs_d || mean_dir), "null pointer");
+    k_get_rays_pose_bw<<<(int)n_images, 256, 0, (hipStream_t)stream>>>(
+        n_rays, directions, poses, dR, img_idxs, pix_idxs, mean_dir, dL_drays_o, dL_drays_d,
+        dL_dimgs_d, dL_ddR, dL_ddT);
     RN_CHECK_LAUNCH();
     return 0;
 }

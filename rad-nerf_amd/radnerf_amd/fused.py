@@ -870,14 +870,21 @@ class FusedMLRenderer:
     def train_step(self, rays_o, rays_d, gate_in2, target_rgb, noise, bg, lambda_opacity=1e-3,
                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0, T_threshold=1e-4,
                    exp_step_factor=0.0, grid_grad=None, mlp_grad=None, gate_grad=None,
-                   lambda_distortion=0.0):
+                   lambda_distortion=0.0, input_grad=False):
         """render -> NeRFLoss -> backward of train_ml.py:179-192 as one launch
         chain: the fused loss kernel writes the backward seeds directly.
         Returns ({term: mean}, (grid_grad, mlp_grad, gate_grad)); gradients are
         accumulated into the given buffers (zero them first).
         lambda_distortion > 0 adds NeRFLoss's distortion term (losses.py:63-67:
         lambda * sum over sub-NeRFs of the per-ray loss's mean) inside the
-        composite kernels: the seed is the constant lambda / B per segment."""
+        composite kernels: the seed is the constant lambda / B per segment.
+        input_grad=True also differentiates the rays (rn_field_dinput +
+        rn_ml_march_bw and the gate's input gradient, the path --optimize_ext
+        needs) and returns a third item (dL/drays_o, dL/drays_d, dL/dgate_in2),
+        (B, 3) each: the first sums the march's and the gate's share, the last
+        is the gradient of the gate's second input alone (add it to dL/drays_d
+        when that input is rays_d).  The last two are views of the workspace:
+        use them before the next backward."""
         from .losses import fused_nerf_loss
         dist = lambda_distortion > 0
         rgb, opacity, depth, gate, imp = self.forward(rays_o, rays_d, gate_in2, noise, bg,
@@ -885,10 +892,19 @@ class FusedMLRenderer:
         terms, (d_rgb, d_op, d_depth, d_gate) = fused_nerf_loss(
             rgb, target_rgb, opacity, depth, gate, imp, lambda_opacity, lambda_cv_importance,
             lambda_depth_mutual, lambda_distortion, self.ws.dist_k if dist else None)
-        grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth, d_gate,
-                              T_threshold, grid_grad, mlp_grad, gate_grad,
-                              float(lambda_distortion) / rays_o.shape[0] if dist else None)
-        return terms, grads
+        d_dist = float(lambda_distortion) / rays_o.shape[0] if dist else None
+        if not input_grad:
+            grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
+                                  d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist)
+            return terms, grads
+        saved, self.input_grad = self.input_grad, True
+        try:
+            grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
+                                  d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist)
+        finally:
+            self.input_grad = saved
+        w = self.ws
+        return terms, grads, (w.drays_o + w.gate_dx[:, 0:3], w.drays_d, w.gate_dx[:, 3:6])
 
 
 class _MLRenderFn(torch.autograd.Function):

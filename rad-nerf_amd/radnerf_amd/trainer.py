@@ -10,6 +10,15 @@ parameters, density grids and bitfields stay bit-identical across ranks.
     for step in range(n):
         terms = tr.step(rays_o, rays_d, imgs_d, target_rgb)
 
+With camera pose refinement (--optimize_ext, train_ml.py:90-93, 129-146) the
+trainer owns the cameras and forms the rays itself from (image, pixel) picks;
+the per-image corrections dR (axis-angle) / dT are parameters of the same
+flat gradient buffer and the same Adam, in a group of their own:
+
+    tr = Trainer(model, gate, n_rays=8192, directions=directions, poses=poses,
+                 optimize_ext=True, pose_lr=1e-8)
+    terms = tr.step_pixels(img_idxs, pix_idxs, target_rgb)
+
 Out of scope: datasets, the Lightning loop, the cosine lr
 schedule (set `tr.opt.param_groups[0]["lr"]` per epoch), logging.
 """
@@ -26,7 +35,13 @@ class Trainer:
     def __init__(self, model, gating_net, n_rays, lr=1e-2, lambda_opacity=1e-3,
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
-                 bucketed=True, lambda_distortion=0.0):
+                 bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
+                 optimize_ext=False, pose_lr=1e-8):
+        if optimize_ext and (directions is None or poses is None):
+            raise ValueError("Trainer(optimize_ext=True) needs directions (P, 3) and poses "
+                             "(N, 3, 4): the pose corrections are per image of `poses`")
+        if (directions is None) != (poses is None):
+            raise ValueError("Trainer: give directions and poses together")
         self.model, self.gate = model, gating_net
         self.device = model.mlp_params.device
         self.renderer = FusedMLRenderer(model, gating_net, n_rays)
@@ -39,11 +54,37 @@ class Trainer:
                             lambda_depth_mutual=lambda_depth_mutual,
                             lambda_distortion=lambda_distortion)
         params = [model.xyz_encoder.params, model.mlp_params, gating_net.params]
+        # the cameras step_pixels forms rays from (train_ml.py:126-127)
+        self.optimize_ext = bool(optimize_ext)
+        self.directions = self.poses = self.mean_dir = None
+        if directions is not None:
+            if directions.ndim != 2 or directions.shape[1] != 3 or poses.ndim != 3 \
+                    or tuple(poses.shape[1:]) != (3, 4):
+                raise ValueError(f"Trainer: directions must be (P, 3) and poses (N, 3, 4), got "
+                                 f"{tuple(directions.shape)} and {tuple(poses.shape)}")
+            self.directions = directions.detach().to(self.device, torch.float32).contiguous()
+            self.poses = poses.detach().to(self.device, torch.float32).contiguous()
+        pose_params = []
+        if self.optimize_ext:
+            # train_ml.py:129-134: per-image axis-angle / translation corrections.
+            # They follow the gate in the flat buffer, so [grid, MLP, gate] and
+            # dist.step_ranges keep their offsets, and the ranks average the
+            # pose gradients in the same collective.
+            n_img = self.poses.shape[0]
+            self.dR = torch.nn.Parameter(torch.zeros(n_img, 3, device=self.device))
+            self.dT = torch.nn.Parameter(torch.zeros(n_img, 3, device=self.device))
+            self.mean_dir = self.directions.mean(0).contiguous()
+            pose_params = [self.dR, self.dT]
         # gradients live in one flat buffer: one collective per step
-        self.grads = rdist.GradAllReduce(params, self.device)
-        for p, v in zip(params, self.grads.views):
+        self.grads = rdist.GradAllReduce(params + pose_params, self.device)
+        for p, v in zip(params + pose_params, self.grads.views):
             p.grad = v
-        self.opt = FusedAdam(params, lr=lr, eps=1e-15)      # train_ml.py:143
+        groups = [dict(params=params)]
+        if pose_params:
+            # train_ml.py:146: FusedAdam([dR, dT], 1e-8) -- the hard-coded lr,
+            # and apex's default eps (the network's 1e-15 is passed explicitly)
+            groups.append(dict(params=pose_params, lr=pose_lr, eps=1e-8))
+        self.opt = FusedAdam(groups, lr=lr, eps=1e-15)      # train_ml.py:143
         self.update_interval, self.warmup_steps, self.seed = update_interval, warmup_steps, seed
         # Adam as the epilogue of a bucketed all-reduce (dist.GradAllReduce.
         # reduce_and_step); False: one collective, a division, then Adam
@@ -60,6 +101,28 @@ class Trainer:
 
     def step(self, rays_o, rays_d, imgs_d, target_rgb, noise=None):
         """One training step on this rank's rays; returns {term: mean} (this rank)."""
+        return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, None)
+
+    def step_pixels(self, img_idxs, pix_idxs, target_rgb, noise=None):
+        """One training step on this rank's (image, pixel) picks of the
+        trainer's cameras (train_ml.py:84-96).  With optimize_ext the rays
+        come from the refined poses (rays.pose_rays), the chain also
+        differentiates the rays, and rn_get_rays_pose_bw writes the dR / dT
+        gradients into their views of the flat buffer before the collective."""
+        from . import rays as R
+        if self.directions is None:
+            raise ValueError("Trainer.step_pixels needs Trainer(directions=..., poses=...)")
+        img_idxs = img_idxs.to(self.device, torch.int64).contiguous()
+        pix_idxs = pix_idxs.to(self.device, torch.int64).contiguous()
+        if not self.optimize_ext:
+            rays_o, rays_d, imgs_d = R.batch_rays(self.directions, self.poses, img_idxs, pix_idxs)
+            return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, None)
+        with torch.no_grad():
+            rays_o, rays_d, imgs_d = R.pose_rays(self.directions, self.poses, self.dR, self.dT,
+                                                 img_idxs, pix_idxs, mean_dir=self.mean_dir)
+        return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, (img_idxs, pix_idxs))
+
+    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks):
         if self.global_step % self.update_interval == 0:
             rdist.update_density_grid(self.model, 0.01 * MAX_SAMPLES / 3 ** 0.5,
                                       self.global_step,
@@ -71,9 +134,23 @@ class Trainer:
         second = imgs_d if self.gate.type == "image" else rays_d
         self.grads.zero()
         v = self.grads.views
-        terms, _ = self.renderer.train_step(rays_o, rays_d, second, target_rgb, noise, self._bg(),
-                                            exp_step_factor=self.esf, grid_grad=v[0],
-                                            mlp_grad=v[1], gate_grad=v[2], **self.lambdas)
+        if picks is None:
+            terms, _ = self.renderer.train_step(rays_o, rays_d, second, target_rgb, noise,
+                                                self._bg(), exp_step_factor=self.esf,
+                                                grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2],
+                                                **self.lambdas)
+        else:
+            from . import rays as R
+            terms, _, (g_o, g_d, g_2) = self.renderer.train_step(
+                rays_o, rays_d, second, target_rgb, noise, self._bg(), exp_step_factor=self.esf,
+                grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2], input_grad=True, **self.lambdas)
+            # the gate's second input is rays_d ("ray") or imgs_d ("image")
+            if self.gate.type == "image":
+                g_i = g_2.contiguous()
+            else:
+                g_d, g_i = g_d + g_2, None
+            R.pose_rays_backward(self.directions, self.poses, self.dR.detach(), picks[0],
+                                 picks[1], self.mean_dir, g_o, g_d, g_i, v[3], v[4])
         if self.bucketed:
             self.grads.reduce_and_step(self.opt)
         else:
