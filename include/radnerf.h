@@ -601,6 +601,44 @@ int rn_get_rays_pose_bw(const float* directions, const float* poses, const float
                         const float* dL_drays_d, const float* dL_dimgs_d, float* dL_ddR,
                         float* dL_ddT, void* stream);
 
+/* ---- whole-image validation (train_ml.py:214-250) ---------------------------
+ * rn_ml_combine_test: the test-time epilogue of ml_rendering.py:65-68,149-153
+ * (background, gate-weighted combine) plus the gated depth of train_ml.py:243,
+ * on rn_render_test's outputs as they are (opacity_k / depth_k [K][n_rays],
+ * rgb_k [K][n_rays][3], no background).  Per ray b, summed over i = 0..K-1 in
+ * that order: rgb = sum g[b,i] (rgb_k[i,b] + bg (1 - op_k[i,b])), opacity =
+ * sum g op_k, depth = sum g depth_k.  Results go to row ray0 + b of the
+ * image-sized outputs rgb (N,3), opacity (N), depth (N) and, if given,
+ * depth_k_out (N,K) (the reference's results['depth']), so a chunk loop fills
+ * one image without copies.  gate (n_rays,K); NULL for K = 1 is a gate of
+ * exactly 1 (a single NGP).  bg: 3 floats on the device.
+ * rn_image_sse: the sum of squared differences of two fp32 arrays, the
+ * sum_squared_error of PeakSignalNoiseRatio(data_range=1) (train_ml.py:64-66,
+ * 222-224): PSNR = 10 log10(n_elems / sse).  out_sse (one device double) is
+ * written; n_elems == 0 writes 0.
+ * rn_ssim: StructuralSimilarityIndexMeasure(data_range=1) (train_ml.py:66,
+ * 226-231) on (H*W, C) row-major interleaved images, C <= 4: Gaussian window
+ * 11 x 11, sigma 1.5, normalised to sum 1; c1 = 0.01^2, c2 = 0.03^2; per pixel
+ * (2 mu_p mu_t + c1)(2 s_pt + c2) / ((mu_p^2 + mu_t^2 + c1)(s_pp + s_tt + c2))
+ * with s_xy = E[xy] - mu_x mu_y, on the valid windows only: an (H-10, W-10)
+ * map per channel.  out_sum (one device double, written) is the sum of the
+ * C (H-10)(W-10) values (divide for the score); ssim_map, if given, is the
+ * (H-10, W-10, C) fp32 map.  pred == target gives exactly 1 per pixel.  H or
+ * W below 11 is an invalid argument.
+ * Both metrics sum per-block partials in a fixed order, in double, without
+ * atomics: two calls give the same bits.  work: RN_METRICS_WORK_BYTES bytes of
+ * device scratch (8-byte aligned), not shared by calls in flight on different
+ * streams.                                                                   */
+#define RN_METRICS_WORK_BYTES 8192
+int rn_ml_combine_test(const float* gate, const float* opacity_k, const float* depth_k,
+                       const float* rgb_k, const float* bg, int64_t n_rays, int32_t n_models,
+                       int64_t ray0, float* rgb, float* opacity, float* depth,
+                       float* depth_k_out /*may be NULL*/, void* stream);
+int rn_image_sse(const float* pred, const float* target, int64_t n_elems, void* work,
+                 double* out_sse, void* stream);
+int rn_ssim(const float* pred, const float* target, int32_t H, int32_t W, int32_t C, void* work,
+            double* out_sum, float* ssim_map /*may be NULL*/, void* stream);
+
 /* ---- parameter packing (f32 master -> f16 MFMA fragments / f16 grid) ------*/
 int rn_pack_f16(const float* src, int64_t src_stride, const int32_t* index, int64_t n,
                 int32_t n_models, int64_t dst_stride, void* dst, void* stream);

@@ -8,6 +8,8 @@ this package is the Python host side mirroring the reference's interfaces:
   rendering          render / ml_render (reference structure)
   fused              single-chain fused ml_render for training
   dist               ray-batch data parallelism over RCCL
+  evaluate           whole-image validation render (ImageEvaluator)
+  metrics            PSNR / SSIM of validation_step on the device
 """
 from ._lib import lib, LIB_PATH  # noqa: F401
 

@@ -92,6 +92,9 @@ SIGNATURES = {
     "rn_get_rays": [P, P, P, P, I64, P, P, P, P, P],
     "rn_get_rays_pose": [P, P, P, P, P, P, I64, P, P, P, P, P],
     "rn_get_rays_pose_bw": [P, P, P, P, P, I64, I64, P, P, P, P, P, P, P],
+    "rn_ml_combine_test": [P, P, P, P, P, I64, I32, I64, P, P, P, P, P],
+    "rn_image_sse": [P, P, I64, P, P, P],
+    "rn_ssim": [P, P, I32, I32, I32, P, P, P, P],
     "rn_pack_f16": [P, I64, P, I64, I32, I64, P, P],
     "rn_to_f16": [P, I64, P, P],
     "rn_morton3d": [P, I64, P, P],
@@ -101,6 +104,7 @@ SIGNATURES = {
 }
 
 ABI_VERSION = 9
+METRICS_WORK_BYTES = 8192       # include/radnerf.h RN_METRICS_WORK_BYTES
 _lib = None
 
 _CODE = {P: "p", I32: "i", I64: "l", F32: "f", F64: "d", U64: "u"}

@@ -19,6 +19,14 @@ flat gradient buffer and the same Adam, in a group of their own:
                  optimize_ext=True, pose_lr=1e-8)
     terms = tr.step_pixels(img_idxs, pix_idxs, target_rgb)
 
+Validation (validation_step, train_ml.py:214-250) renders whole images of the
+trainer's camera on the test-time chain and reports PSNR / SSIM
+(radnerf_amd.evaluate, radnerf_amd.metrics); it leaves the training state alone:
+
+    tr = Trainer(model, gate, n_rays=8192, directions=directions, poses=poses,
+                 img_wh=(W, H))
+    val = tr.validate(test_poses, test_images)      # {"psnr", "ssim", "per_image"}
+
 Out of scope: datasets, the Lightning loop, the cosine lr
 schedule (set `tr.opt.param_groups[0]["lr"]` per epoch), logging.
 """
@@ -36,12 +44,22 @@ class Trainer:
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
-                 optimize_ext=False, pose_lr=1e-8):
+                 optimize_ext=False, pose_lr=1e-8, img_wh=None):
         if optimize_ext and (directions is None or poses is None):
             raise ValueError("Trainer(optimize_ext=True) needs directions (P, 3) and poses "
                              "(N, 3, 4): the pose corrections are per image of `poses`")
         if (directions is None) != (poses is None):
             raise ValueError("Trainer: give directions and poses together")
+        if img_wh is not None:
+            if directions is None:
+                raise ValueError("Trainer(img_wh=...) needs directions and poses: img_wh is the "
+                                 "(W, H) of the camera `directions` describes")
+            if len(img_wh) != 2 or int(img_wh[0]) * int(img_wh[1]) != directions.shape[0]:
+                raise ValueError(f"Trainer: img_wh {tuple(img_wh)} does not match the "
+                                 f"{directions.shape[0]} rows of directions")
+        # validate()'s camera: (W, H) of `directions`
+        self.img_wh = None if img_wh is None else (int(img_wh[0]), int(img_wh[1]))
+        self._evaluator = None
         self.model, self.gate = model, gating_net
         self.device = model.mlp_params.device
         self.renderer = FusedMLRenderer(model, gating_net, n_rays)
@@ -158,3 +176,42 @@ class Trainer:
             self.opt.step()
         self.global_step += 1
         return terms
+
+    def validate(self, poses, images, T_threshold=1e-4):
+        """validation_step (train_ml.py:214-250) over (pose, image) pairs:
+        poses (N, 3, 4) camera-to-world, used as they are (the test split's own
+        poses: no dR / dT, as the reference), images (N, H*W, 3) fp32 (or a
+        sequence of (H*W, 3)) of the trainer's camera.  Returns {"psnr": mean,
+        "ssim": mean, "per_image": [{"psnr", "ssim"}, ...]}, device fp64
+        scalars, with no host synchronisation.  Training state is untouched:
+        no density-grid update, no step.  Each rank evaluates what it is
+        given."""
+        from .evaluate import ImageEvaluator
+        from .metrics import ImageMetrics
+        if self.directions is None or self.img_wh is None:
+            raise ValueError("Trainer.validate needs Trainer(directions=..., poses=..., "
+                             "img_wh=(W, H))")
+        if min(self.img_wh) < 11:
+            raise ValueError(f"Trainer.validate: img_wh {self.img_wh}: SSIM needs H and W of at "
+                             "least 11 (one 11 x 11 window)")
+        if not torch.is_tensor(poses) or poses.ndim != 3 or tuple(poses.shape[1:]) != (3, 4):
+            raise ValueError(f"Trainer.validate: poses must be (N, 3, 4), got "
+                             f"{tuple(getattr(poses, 'shape', ()))}")
+        if len(images) != poses.shape[0]:
+            raise ValueError(f"Trainer.validate: {len(images)} images for {poses.shape[0]} poses")
+        n_pix = self.directions.shape[0]
+        for i, im in enumerate(images):
+            if not torch.is_tensor(im) or tuple(im.shape) != (n_pix, 3):
+                raise ValueError(f"Trainer.validate: images[{i}] must be ({n_pix}, 3), got "
+                                 f"{tuple(getattr(im, 'shape', ()))}")
+            if im.dtype != torch.float32 or not im.is_contiguous():
+                raise ValueError(f"Trainer.validate: images[{i}] must be contiguous float32")
+        if self._evaluator is None:
+            self._evaluator = ImageEvaluator(self.model, self.gate, self.directions, self.img_wh,
+                                             exp_step_factor=self.esf)
+        acc = ImageMetrics()
+        for pose, im in zip(poses, images):
+            im = im.to(self.device)
+            rgb = self._evaluator.render_image(pose, T_threshold)["rgb"]
+            acc.update(rgb, im, self.img_wh)
+        return acc.compute()
