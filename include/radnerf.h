@@ -601,6 +601,45 @@ int rn_get_rays_pose_bw(const float* directions, const float* poses, const float
                         const float* dL_drays_d, const float* dL_dimgs_d, float* dL_ddR,
                         float* dL_ddT, void* stream);
 
+/* ---- a training step's inputs from device-resident images --------------------
+ * rn_sample_batch: datasets/base.py:23-31 (the batch's image and pixel picks,
+ * iid uniform with replacement as np.random.choice, and the target gather) and
+ * train_ml.py:84-96,180 (the rays of those picks, the march jitter, the random
+ * background) in one launch, one thread per ray.  images: (n_images, n_pix, 3)
+ * on the device, uint8 (image_dtype 0; target = (float)v / 255.0f, a division
+ * as torch's u8.float() / 255) or fp32 (image_dtype 1; a bit copy); the element
+ * offset (img n_pix + pix) 3 is 64-bit.  Outputs: img_idxs, pix_idxs (n_rays)
+ * int64 (what rn_get_rays_pose_bw reads), target_rgb, rays_o, rays_d and imgs_d
+ * (n_rays,3), noise (n_models, n_rays) or NULL, bg (3) or NULL.  The rays are
+ * bit-identical to rn_get_rays' on the same picks when dR and dT are both
+ * NULL, and to rn_get_rays_pose's otherwise (dR, dT: NULL or (n_images,3));
+ * imgs_d and mean_dir are NULL together.
+ * The random stream (part of the interface; all arithmetic is uint64, wrapping):
+ *   mix(z): z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;
+ *           z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  return z ^ (z >> 31)
+ *           (the splitmix64 finaliser)
+ *   G = 0x9e3779b97f4a7c15
+ *   key = mix(seed * G + ((uint64)rank << 40 | step))
+ *   pick i:  z = mix(key + (i + 1) * G);
+ *            img = (hi32(z) * n_images) >> 32;  pix = (lo32(z) * n_pix) >> 32
+ *   jitter of (model k, ray i):
+ *            unit(mix((key ^ 0xd1b54a32d192ed03) + (k * n_rays + i + 1) * G))
+ *   background channel c:
+ *            unit(mix((key ^ 0x8cb92ba72f3d8dd7) + (c + 1) * G))
+ *   unit(z) = float(z >> 40) * 2^-24, in [0, 1)
+ * Status 1: step outside [0, 2^40), rank outside [0, 2^24), n_images or n_pix
+ * outside [1, 2^32), image_dtype other than 0 / 1, n_models < 1, a missing
+ * required pointer, imgs_d and mean_dir not both NULL or both given.
+ * n_rays == 0 is a no-op returning 0.  Plain stores, no atomics, no host
+ * synchronisation.                                                           */
+int rn_sample_batch(const void* images, int32_t image_dtype, int64_t n_images, int64_t n_pix,
+                    const float* directions, const float* poses, const float* dR,
+                    const float* dT, const float* mean_dir, uint64_t seed, int64_t step,
+                    int32_t rank, int64_t n_rays, int32_t n_models, int64_t* img_idxs,
+                    int64_t* pix_idxs, float* target_rgb, float* rays_o, float* rays_d,
+                    float* imgs_d /*may be NULL*/, float* noise /*may be NULL*/,
+                    float* bg /*may be NULL*/, void* stream);
+
 /* ---- whole-image validation (train_ml.py:214-250) ---------------------------
  * rn_ml_combine_test: the test-time epilogue of ml_rendering.py:65-68,149-153
  * (background, gate-weighted combine) plus the gated depth of train_ml.py:243,

@@ -328,13 +328,8 @@ k_field_density(FieldArgs a, float* __restrict__ feat_out) {
 // ---------------------------------------------------------------------------
 #define DU_BLK 1024        // cells per counting block (G^3 is a multiple)
 
-__device__ __forceinline__ uint64_t du_mix(uint64_t z) {      // splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
 __device__ __forceinline__ uint32_t du_hash(uint64_t seed, uint32_t seg, uint32_t i, uint32_t st) {
-    return (uint32_t)(du_mix(seed * 0x9e3779b97f4a7c15ull + (((uint64_t)seg << 32) | i) +
+    return (uint32_t)(rn_mix64(seed * 0x9e3779b97f4a7c15ull + (((uint64_t)seg << 32) | i) +
                              (uint64_t)st * 0xd1b54a32d192ed03ull) >> 32);
 }
 __device__ __forceinline__ float du_unit(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }

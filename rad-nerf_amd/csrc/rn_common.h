@@ -105,6 +105,23 @@ __host__ __device__ __forceinline__ uint32_t rn_morton3d_invert(uint32_t x) {
 }
 
 // ---------------------------------------------------------------------------
+// counter-based random streams (the sampled density update, field_aux.hip, and
+// the batch sampler, sample.hip): the splitmix64 finaliser, and the 24-bit
+// unit float of a 64-bit word's top bits, in [0, 1)
+// ---------------------------------------------------------------------------
+#define RN_GOLDEN64 0x9e3779b97f4a7c15ull
+
+__host__ __device__ __forceinline__ uint64_t rn_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+__host__ __device__ __forceinline__ float rn_unit64(uint64_t z) {
+    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+}
+
+// ---------------------------------------------------------------------------
 // wave64 collectives
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int rn_lane() { return threadIdx.x & (RN_WAVE - 1); }

@@ -11,6 +11,7 @@
 //    over the flat fp32 parameter buffer, one pass that also refreshes the f16
 //    copy of the hash table the field kernels gather from.
 #include "rn_common.h"
+#include "rn_rays.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -124,8 +125,8 @@ k_adam(int64_t n, float* __restrict__ p, const float* __restrict__ g, float* __r
 }
 
 // train_ml.py:84-96 + datasets/ray_utils.py:45-70 (get_rays) for a batch of
-// (image, pixel) picks: rays_d = R dir, rays_o = T, imgs_d = R mean_dir.
-// The 3x3 rotation is applied as three dot products in (x, y, z) order.
+// (image, pixel) picks: rays_d = R dir, rays_o = T, imgs_d = R mean_dir
+// (rn_rays.h rn_rays_plain, shared with the batch sampler).
 __global__ void __launch_bounds__(256)
 k_get_rays(int64_t n, const float* __restrict__ dirs, const float* __restrict__ poses,
            const int64_t* __restrict__ img_idx, const int64_t* __restrict__ pix_idx,
@@ -135,69 +136,11 @@ k_get_rays(int64_t n, const float* __restrict__ dirs, const float* __restrict__ 
     if (r >= n) return;
     const float* P = poses + 12 * (img_idx ? img_idx[r] : 0);     // (3, 4) row-major
     const float* d = dirs + 3 * (pix_idx ? pix_idx[r] : r);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        rays_d[3 * r + i] = d[0] * P[4 * i] + d[1] * P[4 * i + 1] + d[2] * P[4 * i + 2];
-        rays_o[3 * r + i] = P[4 * i + 3];
-        if (imgs_d)
-            imgs_d[3 * r + i] = mean_dir[0] * P[4 * i] + mean_dir[1] * P[4 * i + 1] +
-                                mean_dir[2] * P[4 * i + 2];
-    }
+    rn_rays_plain(r, P, d, mean_dir, rays_o, rays_d, imgs_d);
 }
 
-// ---- pose refinement (--optimize_ext: train_ml.py:90-93, ray_utils.py:73-100)
-// Rodrigues coefficients of A(v) = I + a K + b K^2 at theta = |v| + 1e-7 and
-// their derivatives in theta.  fp32: below theta = 1e-2 the closed forms cancel
-// (theta cos - sin ~ theta^3 / 3 out of terms of size theta), so the Taylor
-// series take over there (next terms theta^4 / 120 and smaller); above it
-// 1 - cos is formed as 2 sin^2(theta / 2), which does not cancel.
-struct RodCoef { float a, b, da, db; };
-
-__device__ inline RodCoef rod_coef(float th) {
-    RodCoef c;
-    const float t2 = th * th;
-    if (th < 1e-2f) {
-        c.a = 1.0f - t2 / 6.0f;
-        c.b = 0.5f - t2 / 24.0f;
-        c.da = -th / 3.0f + th * t2 / 30.0f;
-        c.db = -th / 12.0f + th * t2 / 180.0f;
-    } else {
-        const float s = sinf(th), co = cosf(th), sh = sinf(0.5f * th);
-        const float omc = 2.0f * sh * sh;                  // 1 - cos(theta)
-        c.a = s / th;
-        c.b = omc / t2;
-        c.da = (th * co - s) / t2;
-        c.db = (th * s - 2.0f * omc) / (t2 * th);
-    }
-    return c;
-}
-
-// K = skew(v), row-major 3x3
-__device__ inline void skew3(const float* v, float* K) {
-    K[0] = 0.f;   K[1] = -v[2]; K[2] = v[1];
-    K[3] = v[2];  K[4] = 0.f;   K[5] = -v[0];
-    K[6] = -v[1]; K[7] = v[0];  K[8] = 0.f;
-}
-
-__device__ inline void mm3(const float* X, const float* Y, float* Z) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Z[3 * i + j] = X[3 * i] * Y[j] + X[3 * i + 1] * Y[3 + j] + X[3 * i + 2] * Y[6 + j];
-}
-
-__device__ inline float dot9(const float* X, const float* Y) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) s += X[i] * Y[i];
-    return s;
-}
-
-// k_get_rays with the per-image refinement applied first: R = A(dR[n]) R0,
-// T = T0 + dT[n] (the rotation is not applied to the translation, as in the
-// reference).  R is then applied with k_get_rays' dot products, so zero dR /
-// dT (A = I exactly) reproduce its outputs.
+// k_get_rays with the per-image refinement applied first (--optimize_ext:
+// train_ml.py:90-93, ray_utils.py:73-100; rn_rays.h rn_rays_pose).
 __global__ void __launch_bounds__(256)
 k_get_rays_pose(int64_t n, const float* __restrict__ dirs, const float* __restrict__ poses,
                 const float* __restrict__ dR, const float* __restrict__ dT,
@@ -209,33 +152,7 @@ k_get_rays_pose(int64_t n, const float* __restrict__ dirs, const float* __restri
     const int64_t im = img_idx[r];
     const float* P = poses + 12 * im;                             // (3, 4) row-major
     const float* d = dirs + 3 * (pix_idx ? pix_idx[r] : r);
-    float R[9];
-    if (dR) {
-        const float v[3] = {dR[3 * im], dR[3 * im + 1], dR[3 * im + 2]};
-        const float th = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) + 1e-7f;
-        const RodCoef c = rod_coef(th);
-        float K[9], K2[9], A[9], R0[9];
-        skew3(v, K);
-        mm3(K, K, K2);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            A[i] = ((i % 4 == 0) ? 1.0f : 0.0f) + (c.a * K[i] + c.b * K2[i]);
-            R0[i] = P[4 * (i / 3) + i % 3];
-        }
-        mm3(A, R0, R);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = P[4 * (i / 3) + i % 3];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        rays_d[3 * r + i] = d[0] * R[3 * i] + d[1] * R[3 * i + 1] + d[2] * R[3 * i + 2];
-        const float T0 = P[4 * i + 3];
-        rays_o[3 * r + i] = dT ? T0 + dT[3 * im + i] : T0;
-        if (imgs_d)
-            imgs_d[3 * r + i] = mean_dir[0] * R[3 * i] + mean_dir[1] * R[3 * i + 1] +
-                                mean_dir[2] * R[3 * i + 2];
-    }
+    rn_rays_pose(r, im, P, d, dR, dT, mean_dir, rays_o, rays_d, imgs_d);
 }
 
 // Backward of k_get_rays_pose into dL/ddR, dL/ddT: one 256-thread block per

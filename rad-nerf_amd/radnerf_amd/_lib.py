@@ -92,6 +92,8 @@ SIGNATURES = {
     "rn_get_rays": [P, P, P, P, I64, P, P, P, P, P],
     "rn_get_rays_pose": [P, P, P, P, P, P, I64, P, P, P, P, P],
     "rn_get_rays_pose_bw": [P, P, P, P, P, I64, I64, P, P, P, P, P, P, P],
+    "rn_sample_batch": [P, I32, I64, I64, P, P, P, P, P, U64, I64, I32, I64, I32, P, P, P, P, P,
+                        P, P, P, P],
     "rn_ml_combine_test": [P, P, P, P, P, I64, I32, I64, P, P, P, P, P],
     "rn_image_sse": [P, P, I64, P, P, P],
     "rn_ssim": [P, P, I32, I32, I32, P, P, P, P],

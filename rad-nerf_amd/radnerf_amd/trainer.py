@@ -27,9 +27,34 @@ trainer's camera on the test-time chain and reports PSNR / SSIM
                  img_wh=(W, H))
     val = tr.validate(test_poses, test_images)      # {"psnr", "ssim", "per_image"}
 
-Out of scope: datasets, the Lightning loop, the cosine lr
-schedule (set `tr.opt.param_groups[0]["lr"]` per epoch), logging.
+With the training images on the device (uint8 or fp32, sampler.TrainImages)
+the trainer also produces each step's inputs and runs the epoch loop
+(datasets/base.py:23-31, train_ml.py:124-153,172-200,295-297):
+
+    tr = Trainer(model, gate, n_rays=8192, directions=directions, poses=poses,
+                 img_wh=(W, H), images=images_u8)        # (N, H*W, 3)
+    terms = tr.step_sampled()         # one rn_sample_batch launch, then the step
+    log = tr.fit(num_epochs=30, steps_per_epoch=1000, val_poses=test_poses,
+                 val_images=test_images)
+
+step_sampled draws the (image, pixel) picks, gathers the targets, forms the
+rays (refined by dR / dT under optimize_ext) and fills the march jitter and
+the random background in one launch, all from a counter-based hash of
+(seed, global_step, rank): no torch generator, different pixels on every
+rank, and a trainer resumed with the same seed and global_step continues the
+same stream.  The consumed batch stays in `tr.last_batch`.  step and
+step_pixels keep drawing from torch's generator.  fit sets the cosine
+schedule (sampler.cosine_lr, eta_min = lr / 30) on the network's parameter
+group at each epoch's start (the pose group keeps its lr, as the reference
+schedules only net_opt), accumulates the epoch's loss terms on the device,
+reads them once per epoch for the log, and validates every `val_every` epochs
+and after the last.
+
+Out of scope: dataset file readers, the Lightning loop,
+logging back-ends.
 """
+import math
+
 import torch
 
 from . import dist as rdist
@@ -39,12 +64,18 @@ from .optim import FusedAdam
 MAX_SAMPLES = 1024
 
 
+def _rank():
+    """torch.distributed's rank when it is initialised, else 0"""
+    import torch.distributed as td
+    return td.get_rank() if td.is_available() and td.is_initialized() else 0
+
+
 class Trainer:
     def __init__(self, model, gating_net, n_rays, lr=1e-2, lambda_opacity=1e-3,
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
-                 optimize_ext=False, pose_lr=1e-8, img_wh=None):
+                 optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None):
         if optimize_ext and (directions is None or poses is None):
             raise ValueError("Trainer(optimize_ext=True) needs directions (P, 3) and poses "
                              "(N, 3, 4): the pose corrections are per image of `poses`")
@@ -57,6 +88,20 @@ class Trainer:
             if len(img_wh) != 2 or int(img_wh[0]) * int(img_wh[1]) != directions.shape[0]:
                 raise ValueError(f"Trainer: img_wh {tuple(img_wh)} does not match the "
                                  f"{directions.shape[0]} rows of directions")
+        if images is not None:
+            from .sampler import TrainImages
+            if directions is None:
+                raise ValueError("Trainer(images=...) needs directions and poses: the images "
+                                 "are those of `poses`, pixel by pixel of `directions`")
+            if not isinstance(images, TrainImages):
+                images = TrainImages(images)
+            if images.n_images != poses.shape[0] or images.n_pix != directions.shape[0]:
+                raise ValueError(f"Trainer: images are {images.n_images} x {images.n_pix} pixels "
+                                 f"for {poses.shape[0]} poses and {directions.shape[0]} rows of "
+                                 "directions")
+        # step_sampled()'s training set and its reused batch buffers
+        self.images, self.last_batch = images, None
+        self.n_rays, self.lr0 = int(n_rays), float(lr)
         # validate()'s camera: (W, H) of `directions`
         self.img_wh = None if img_wh is None else (int(img_wh[0]), int(img_wh[1]))
         self._evaluator = None
@@ -140,7 +185,33 @@ class Trainer:
                                                  img_idxs, pix_idxs, mean_dir=self.mean_dir)
         return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, (img_idxs, pix_idxs))
 
-    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks):
+    def step_sampled(self, noise=None):
+        """One training step on a batch the trainer draws itself from its
+        device-resident images (Trainer(images=...)): sampler.sample_batch for
+        the key (seed, global_step, rank) -- picks, targets, rays (refined
+        under optimize_ext), march jitter, random background in one launch --
+        then the step of step_pixels.  `noise` overrides the sampled jitter.
+        The consumed batch is kept as self.last_batch (its buffers are reused
+        by the next call)."""
+        from .sampler import sample_batch
+        if self.images is None:
+            raise ValueError("Trainer.step_sampled needs Trainer(images=..., directions=..., "
+                             "poses=...)")
+        if self.mean_dir is None and self.gate.type == "image":
+            self.mean_dir = self.directions.mean(0).contiguous()
+        ext = self.optimize_ext
+        b = self.last_batch = sample_batch(
+            self.images, self.directions, self.poses, self.n_rays, self.model.size, self.seed,
+            self.global_step, rank=_rank(),
+            dR=self.dR.detach() if ext else None, dT=self.dT.detach() if ext else None,
+            mean_dir=self.mean_dir if self.gate.type == "image" else None, out=self.last_batch)
+        # ml_rendering.py:192-198: the random background only with exp stepping
+        bg = b["bg"] if self.random_bg and self.esf != 0 else self._bg()
+        return self._step(b["rays_o"], b["rays_d"], b["imgs_d"], b["target"],
+                          b["noise"] if noise is None else noise,
+                          (b["img_idxs"], b["pix_idxs"]) if ext else None, bg)
+
+    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks, bg=None):
         if self.global_step % self.update_interval == 0:
             rdist.update_density_grid(self.model, 0.01 * MAX_SAMPLES / 3 ** 0.5,
                                       self.global_step,
@@ -150,17 +221,19 @@ class Trainer:
         if noise is None:
             noise = torch.rand(K, B, device=self.device)
         second = imgs_d if self.gate.type == "image" else rays_d
+        if bg is None:
+            bg = self._bg()
         self.grads.zero()
         v = self.grads.views
         if picks is None:
             terms, _ = self.renderer.train_step(rays_o, rays_d, second, target_rgb, noise,
-                                                self._bg(), exp_step_factor=self.esf,
+                                                bg, exp_step_factor=self.esf,
                                                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2],
                                                 **self.lambdas)
         else:
             from . import rays as R
             terms, _, (g_o, g_d, g_2) = self.renderer.train_step(
-                rays_o, rays_d, second, target_rgb, noise, self._bg(), exp_step_factor=self.esf,
+                rays_o, rays_d, second, target_rgb, noise, bg, exp_step_factor=self.esf,
                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2], input_grad=True, **self.lambdas)
             # the gate's second input is rays_d ("ray") or imgs_d ("image")
             if self.gate.type == "image":
@@ -215,3 +288,61 @@ class Trainer:
             rgb = self._evaluator.render_image(pose, T_threshold)["rgb"]
             acc.update(rgb, im, self.img_wh)
         return acc.compute()
+
+    def fit(self, num_epochs=30, steps_per_epoch=1000, val_poses=None, val_images=None,
+            val_every=None, eta_min=None, callback=None):
+        """The epoch loop of train_ml.py:124-153,172-200,295-297 on the
+        trainer's device-resident images.  At the start of epoch e the
+        network's parameter group gets sampler.cosine_lr(lr, e, num_epochs,
+        eta_min) (eta_min None: lr / 30; the pose group keeps its lr); the
+        epoch runs steps_per_epoch step_sampled() calls, summing the loss terms
+        on the device, and reads them once at its end.  With val_poses /
+        val_images (as validate takes them) the validation runs every
+        val_every epochs (None: min(num_epochs, 10), as
+        check_val_every_n_epoch) and after the last.  Returns one dict per
+        epoch: epoch, lr, loss (the sum of the term means), terms {name: mean},
+        train_psnr (-10 log10 of the epoch's mean rgb MSE, what the accumulated
+        PeakSignalNoiseRatio(data_range=1) logs) and, where it ran, val
+        {"psnr", "ssim"} as floats.  callback(entry) is called once per epoch.
+        The batches depend on (seed, global_step, rank) alone: a trainer
+        resumed with the same seed and global_step continues the stream."""
+        from .sampler import cosine_lr
+        if self.images is None:
+            raise ValueError("Trainer.fit needs Trainer(images=..., directions=..., poses=...)")
+        num_epochs, steps = int(num_epochs), int(steps_per_epoch)
+        if num_epochs < 1 or steps < 1:
+            raise ValueError(f"Trainer.fit: num_epochs and steps_per_epoch must be at least 1, "
+                             f"got {num_epochs} and {steps}")
+        if (val_poses is None) != (val_images is None):
+            raise ValueError("Trainer.fit: give val_poses and val_images together")
+        if val_poses is not None and self.img_wh is None:
+            raise ValueError("Trainer.fit(val_poses=...) needs Trainer(img_wh=(W, H))")
+        val_every = min(num_epochs, 10) if val_every is None else int(val_every)
+        if val_every < 1:
+            raise ValueError(f"Trainer.fit: val_every must be at least 1, got {val_every}")
+        if callback is not None and not callable(callback):
+            raise ValueError("Trainer.fit: callback must be callable")
+        log = []
+        for epoch in range(num_epochs):
+            lr = cosine_lr(self.lr0, epoch, num_epochs, eta_min)
+            self.opt.param_groups[0]["lr"] = lr
+            names, acc = None, None
+            for _ in range(steps):
+                terms = self.step_sampled()
+                if names is None:
+                    names = list(terms)
+                    acc = torch.zeros(len(names), device=self.device, dtype=torch.float64)
+                acc += torch.stack([terms[k] for k in names])
+            means = (acc / steps).tolist()              # the epoch's one host read
+            terms = dict(zip(names, means))
+            entry = {"epoch": epoch, "lr": lr, "loss": sum(means), "terms": terms,
+                     "train_psnr": -10.0 * math.log10(terms["rgb"]) if terms["rgb"] > 0
+                     else math.inf}
+            if val_poses is not None and ((epoch + 1) % val_every == 0
+                                          or epoch == num_epochs - 1):
+                val = self.validate(val_poses, val_images)
+                entry["val"] = {k: float(val[k]) for k in ("psnr", "ssim")}
+            log.append(entry)
+            if callback is not None:
+                callback(entry)
+        return log
