@@ -538,6 +538,27 @@ int rn_density_update_sampled(const void* grid_ptrs, const void* bitfield_ptrs, 
                               const void* frags, float* tmp, int32_t* occ, int32_t* blk,
                               float* part, float* thr_out, int32_t all_cells,
                               void* stream);
+/* rn_density_update_sampled on a grid culled by rn_mark_invisible_cells (same
+ * kernels, same arguments, two more).  A cell whose density is negative is
+ * never listed: not by the uniform draw, not by the occupied draw, not by the
+ * warm-up's "every cell"; its tmp stays 0 and no sigma is evaluated for it.
+ * erode != 0 (networks.py:396-398) needs count_grid ((cascades, 128^3) f32,
+ * rn_mark_invisible_cells; status 1 without it): the decay of a cell is then
+ * clamp(powf(decay, 1.0f / count), 0.1f, 0.95f) instead of decay.  With
+ * erode == 0 count_grid may be NULL and is not read, and the density grids,
+ * thr_out and bitfields left behind are bit-identical to
+ * rn_density_update_sampled's for the same seed, whether or not the grid
+ * holds negative cells (those keep their value in both); only tmp at the
+ * negative cells differs.                                                    */
+int rn_density_update_visible(const void* grid_ptrs, const void* bitfield_ptrs, int32_t n_models,
+                              int32_t cascades, int32_t grid_size, float scale,
+                              float density_threshold, float decay, uint64_t seed,
+                              const void* grid_f16, const uint32_t* level_offset,
+                              const uint32_t* level_hsize, const uint32_t* level_res,
+                              const float* level_scale, const float* xyz_min, const float* extent,
+                              const void* frags, float* tmp, int32_t* occ, int32_t* blk,
+                              float* part, float* thr_out, int32_t all_cells,
+                              const float* count_grid, int32_t erode, void* stream);
 int rn_field_density(const float* xyzs, int64_t n_samples, const void* grid_f16,
                      const uint32_t* level_offset, const uint32_t* level_hsize,
                      const uint32_t* level_res, const float* level_scale, const float* xyz_min,
@@ -694,6 +715,42 @@ int rn_packbits(const float* density_grid, int64_t n_bytes, float density_thresh
  * index_put keeps an arbitrary one of them).                                */
 int rn_scatter_max(const int64_t* indices, const float* values, int64_t n, float* out,
                    void* stream);
+/* Camera-visibility culling of the occupancy grids (upstream ngp_pl's
+ * mark_invisible_cells; fills the count_grid that the erode line,
+ * networks.py:396-398, divides by).  poses: (n_cams, 3, 4) c2w f32 on the
+ * device, camera axes right / down / front (ray_utils.py:8-42); one pinhole
+ * fx, fy, cx, cy and width x height for all cameras.  grid_ptrs /
+ * bitfield_ptrs, n_models, cascades, grid_size (128), scale: as
+ * rn_density_update_sampled.  No host synchronisation; status 1 for null or
+ * invalid arguments (n_cams == 0 is one).
+ * The operation order is part of the interface.  Everything is fp32, every
+ * multiply and add rounded on its own (no fused multiply-add).  With
+ * G = grid_size, per cascade c and Morton cell m of inverse Morton
+ * coordinates (i_0, i_1, i_2) (rn_morton3d_invert of m, m >> 1, m >> 2):
+ *   sc  = min(2^(c-1), scale);  hgs = sc / G
+ *   X_a = ((i_a / (G-1)) * 2 - 1) * (sc - hgs)          (the cell centre)
+ * and per camera [R | T] (R[i][j] = pose[4 i + j], T_i = pose[4 i + 3]),
+ * with d_j = X_j - T_j:
+ *   xc = (R[0][0]*d_0 + R[1][0]*d_1) + R[2][0]*d_2
+ *   yc, zc: the same with column 1, column 2 of R
+ *   px = fx*xc + cx*zc;  py = fy*yc + cy*zc
+ *   in_image = zc > 0 && px >= 0 && px < W*zc && py >= 0 && py < H*zc
+ *              (W, H = (float)width, (float)height; no division)
+ *   covered  = in_image && zc >= near_distance
+ *   too_near = in_image && zc <  near_distance
+ * count_grid[c][m] = (float)n_covered / (float)n_cams, written for every cell
+ * ((cascades, 128^3) f32, Morton order).  A cell is valid iff n_covered > 0
+ * and no camera has it too near.  In each of the n_models grids a valid cell
+ * keeps a value >= 0 and becomes 0 if it was negative, its bitfield bit is
+ * left alone; an invalid cell becomes -1 and its bit is cleared.  The call is
+ * idempotent (safe after a checkpoint load).  n_culled (may be NULL):
+ * [cascades] i32, zeroed by the call, the number of invalid cells per
+ * cascade.                                                                   */
+int rn_mark_invisible_cells(const float* poses, int32_t n_cams, float fx, float fy, float cx,
+                            float cy, int32_t width, int32_t height, float near_distance,
+                            const void* grid_ptrs, const void* bitfield_ptrs, int32_t n_models,
+                            int32_t cascades, int32_t grid_size, float scale, float* count_grid,
+                            int32_t* n_culled, void* stream);
 
 #ifdef __cplusplus
 }

@@ -352,6 +352,7 @@ struct DensityUpd {
     int K, C, G, M;
     int all;                        // warm-up: every cell drawn
     float thr, decay, scale;
+    const float* count;             // (C, G3) covering-camera share (rn_density_update_visible)
 };
 #define DU_PART 512
 
@@ -410,8 +411,9 @@ __device__ __forceinline__ float du_lam_occ(const DensityUpd& u, int64_t seg, in
 }
 
 // 3. per-block count of drawn cells.  MODE 0: counts -> dblk; MODE 1: the
-// ordered list (each lane writes its cell at its prefix position)
-template <int MODE>
+// ordered list (each lane writes its cell at its prefix position).  VIS
+// (rn_density_update_visible): a cell with negative density is never listed
+template <int MODE, bool VIS>
 __global__ void __launch_bounds__(256)
 k_du_draws(DensityUpd u, int64_t cap) {
     const int64_t G3 = (int64_t)u.G * u.G * u.G, seg_blocks = G3 / DU_BLK;
@@ -425,7 +427,8 @@ k_du_draws(DensityUpd u, int64_t cap) {
     int total = 0;
     for (int j = 0; j < DU_BLK; j += blockDim.x) {
         const uint32_t cell = (uint32_t)(j0 + j + threadIdx.x);
-        const int n = du_drawn(u, seg, cell, g[j + threadIdx.x] > u.thr, lam_o) ? 1 : 0;
+        const float d = g[j + threadIdx.x];
+        const int n = !(VIS && d < 0.f) && du_drawn(u, seg, cell, d > u.thr, lam_o) ? 1 : 0;
         if (MODE == 0) { total += n; continue; }
         const int incl = rn_wave_incl_sum_i(n);
         const int w = threadIdx.x / RN_WAVE;
@@ -508,7 +511,10 @@ k_du_sample(FieldArgs a, DensityUpd u, int64_t cap) {
 }
 
 // 5. grid = dg < 0 ? dg : max(dg * decay, tmp) in place; per-block partial sum
-// and count of the positive cells (fixed slots: the mean is deterministic)
+// and count of the positive cells (fixed slots: the mean is deterministic).
+// ERODE (networks.py:396-398): per cell clamp(decay^(1 / count), 0.1, 0.95)
+// instead of decay
+template <bool ERODE>
 __global__ void __launch_bounds__(256)
 k_du_decay(DensityUpd u) {
     const int k = blockIdx.y;
@@ -519,7 +525,9 @@ k_du_decay(DensityUpd u) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n;
          e += (int64_t)gridDim.x * blockDim.x) {
         const float d = g[e];
-        const float v = d < 0.f ? d : fmaxf(d * u.decay, t[e]);
+        float decay = u.decay;
+        if (ERODE) decay = fminf(fmaxf(powf(u.decay, 1.0f / u.count[e]), 0.1f), 0.95f);
+        const float v = d < 0.f ? d : fmaxf(d * decay, t[e]);
         g[e] = v;
         if (v > 0.f) { s += v; cnt += 1.f; }
     }
@@ -565,6 +573,47 @@ k_du_pack(DensityUpd u) {
 }
 
 inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
+
+// the launches of rn_density_update_sampled (VIS false) and
+// rn_density_update_visible (VIS true; u.count non-NULL selects the erode decay)
+template <bool VIS>
+hipError_t du_launch(const FieldArgs& a, const DensityUpd& u, hipStream_t st) {
+    const int64_t G3 = (int64_t)u.G * u.G * u.G;
+    const int64_t n_all = (int64_t)u.K * u.C * G3;
+    const int nb = (int)(n_all / DU_BLK);
+    const hipError_t e = hipMemsetAsync(u.tmp, 0, sizeof(float) * n_all, st);
+    if (e != hipSuccess) return e;
+    k_du_count<<<nb, 256, 0, st>>>(u);
+    k_du_scan<<<1, 1024, 0, st>>>(u.blk, nb);
+    k_du_draws<0, VIS><<<nb, 256, 0, st>>>(u, n_all);
+    k_du_scan<<<1, 1024, 0, st>>>(u.dblk, nb);
+    k_du_draws<1, VIS><<<nb, 256, 0, st>>>(u, n_all);
+    // drawn cells: at most 2 M per (sub-NeRF, cascade) on average (1 - e^-1/4
+    // of G^3 plus the occupied ones); the kernel strides over the device count
+    const int64_t tiles = ((u.all ? G3 : 2 * (int64_t)u.M) * u.C + 31) / 32;
+    const int sb = (int)(tiles / 4 + 1 < 2048 ? tiles / 4 + 1 : 2048);
+    k_du_sample<<<dim3(sb, u.K), 256, 0, st>>>(a, u, n_all);
+    if (VIS && u.count) k_du_decay<true><<<dim3(DU_PART, u.K), 256, 0, st>>>(u);
+    else k_du_decay<false><<<dim3(DU_PART, u.K), 256, 0, st>>>(u);
+    k_du_mean<<<u.K, 64, 0, st>>>(u);
+    k_du_pack<<<dim3(nblk(u.C * G3 / 8, 256), u.K), 256, 0, st>>>(u);
+    return hipSuccess;
+}
+
+void du_fill(DensityUpd& u, const void* grid_ptrs, const void* bitfield_ptrs, int32_t n_models,
+             int32_t cascades, int32_t grid_size, float scale, float density_threshold,
+             float decay, uint64_t seed, float* tmp, int32_t* occ, int32_t* blk, float* part,
+             float* thr_out, int32_t all_cells) {
+    const int64_t G3 = (int64_t)grid_size * grid_size * grid_size;
+    const int nb = (int)((int64_t)n_models * cascades * G3 / DU_BLK);
+    u.grids = (const float* const*)grid_ptrs; u.bitfields = (uint8_t* const*)bitfield_ptrs;
+    u.tmp = tmp; u.list = (uint32_t*)occ; u.blk = blk; u.dblk = blk + nb + 1;
+    u.part = part; u.thr_out = thr_out;
+    u.seed = seed; u.K = n_models; u.C = cascades; u.G = grid_size;
+    u.M = (int)(G3 / 4);                                  // networks.py:378: grid_size**3 // 4
+    u.thr = density_threshold; u.decay = decay; u.scale = scale;
+    u.all = all_cells != 0;
+}
 
 }  // namespace
 
@@ -624,35 +673,43 @@ int rn_density_update_sampled(const void* grid_ptrs, const void* bitfield_ptrs, 
     FieldArgs a{};
     fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
     a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
-    const int64_t G3 = (int64_t)grid_size * grid_size * grid_size;
-    const int64_t n_all = (int64_t)n_models * cascades * G3;
-    const int nb = (int)(n_all / DU_BLK);
     DensityUpd u{};
-    u.grids = (const float* const*)grid_ptrs; u.bitfields = (uint8_t* const*)bitfield_ptrs;
-    u.tmp = tmp; u.list = (uint32_t*)occ; u.blk = blk; u.dblk = blk + nb + 1;
-    u.part = part; u.thr_out = thr_out;
-    u.seed = seed; u.K = n_models; u.C = cascades; u.G = grid_size;
-    u.M = (int)(G3 / 4);                                  // networks.py:378: grid_size**3 // 4
-    u.thr = density_threshold; u.decay = decay; u.scale = scale;
-    u.all = all_cells != 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(tmp, 0, sizeof(float) * n_all, st) != hipSuccess) {
+    du_fill(u, grid_ptrs, bitfield_ptrs, n_models, cascades, grid_size, scale, density_threshold,
+            decay, seed, tmp, occ, blk, part, thr_out, all_cells);
+    if (du_launch<false>(a, u, (hipStream_t)stream) != hipSuccess) {
         rn_set_error("%s: memset failed", __func__);
         return 2;
     }
-    k_du_count<<<nb, 256, 0, st>>>(u);
-    k_du_scan<<<1, 1024, 0, st>>>(u.blk, nb);
-    k_du_draws<0><<<nb, 256, 0, st>>>(u, n_all);
-    k_du_scan<<<1, 1024, 0, st>>>(u.dblk, nb);
-    k_du_draws<1><<<nb, 256, 0, st>>>(u, n_all);
-    // drawn cells: at most 2 M per (sub-NeRF, cascade) on average (1 - e^-1/4
-    // of G^3 plus the occupied ones); the kernel strides over the device count
-    const int64_t tiles = ((all_cells ? G3 : 2 * (int64_t)u.M) * cascades + 31) / 32;
-    const int sb = (int)(tiles / 4 + 1 < 2048 ? tiles / 4 + 1 : 2048);
-    k_du_sample<<<dim3(sb, n_models), 256, 0, st>>>(a, u, n_all);
-    k_du_decay<<<dim3(DU_PART, n_models), 256, 0, st>>>(u);
-    k_du_mean<<<n_models, 64, 0, st>>>(u);
-    k_du_pack<<<dim3(nblk(cascades * G3 / 8, 256), n_models), 256, 0, st>>>(u);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_density_update_visible(const void* grid_ptrs, const void* bitfield_ptrs, int32_t n_models,
+                              int32_t cascades, int32_t grid_size, float scale,
+                              float density_threshold, float decay, uint64_t seed,
+                              const void* grid_f16, const uint32_t* level_offset,
+                              const uint32_t* level_hsize, const uint32_t* level_res,
+                              const float* level_scale, const float* xyz_min, const float* extent,
+                              const void* frags, float* tmp, int32_t* occ, int32_t* blk,
+                              float* part, float* thr_out, int32_t all_cells,
+                              const float* count_grid, int32_t erode, void* stream) {
+    RN_CHECK_ARG(n_models >= 1 && cascades >= 1 && cascades <= 32 && grid_size == 128,
+                 "bad sizes (grid_size 128, cascades <= 32)");
+    RN_CHECK_ARG(grid_ptrs && bitfield_ptrs && grid_f16 && level_offset && level_hsize &&
+                 level_res && level_scale && xyz_min && extent && frags && tmp && occ && blk &&
+                 part && thr_out, "null pointer");
+    RN_CHECK_ARG(!erode || count_grid, "erode needs count_grid (rn_mark_invisible_cells)");
+    FieldArgs a{};
+    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
+    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    DensityUpd u{};
+    du_fill(u, grid_ptrs, bitfield_ptrs, n_models, cascades, grid_size, scale, density_threshold,
+            decay, seed, tmp, occ, blk, part, thr_out, all_cells);
+    u.count = erode ? count_grid : nullptr;
+    if (du_launch<true>(a, u, (hipStream_t)stream) != hipSuccess) {
+        rn_set_error("%s: memset failed", __func__);
+        return 2;
+    }
     RN_CHECK_LAUNCH();
     return 0;
 }

@@ -60,6 +60,74 @@ k_scatter_max(int64_t n, const int64_t* __restrict__ idx, const float* __restric
     atomicMax(reinterpret_cast<int*>(out) + idx[i], __float_as_int(fmaxf(v[i], 0.0f)));
 }
 
+struct MarkArgs {
+    const float* poses;             // (n_cams, 3, 4) c2w, columns right / down / front / eye
+    float* const* grids;            // [K] -> (C, G3) density grids
+    uint8_t* const* bitfields;      // [K] -> C G3 / 8 bytes
+    float* count;                   // (C, G3) share of the cameras that cover the cell
+    int32_t* n_culled;              // [C] or NULL
+    int n_cams, K, G;
+    float fx, fy, cx, cy, w, h, near, scale;
+};
+
+// Camera-visibility culling (radnerf.h rn_mark_invisible_cells states the
+// operation order).  One thread per Morton cell, a block inside one cascade
+// (G^3 is a multiple of 256); the camera index is wave-uniform, so the 12 pose
+// floats are uniform loads.  Every camera is visited: the covered count and
+// the any-too-near flag both need all of them.  The wave's 64 consecutive
+// cells are 8 bitfield bytes: a ballot of the invalid lanes, and lane 8 i
+// clears byte i's bits with a plain read-modify-write (no other thread of the
+// launch touches that byte).
+__global__ void __launch_bounds__(256)
+k_mark_invisible(MarkArgs a) {
+    const int64_t G3 = (int64_t)a.G * a.G * a.G;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // < C G3 by the grid
+    const int c = (int)(e / G3);
+    const uint32_t m = (uint32_t)(e - (int64_t)c * G3);
+    const float sc = fminf(scalbnf(1.0f, c - 1), a.scale);
+    const float hgs = sc / a.G;
+    const float gm1 = (float)(a.G - 1);
+    const float X0 = (((float)rn_morton3d_invert(m) / gm1) * 2.0f - 1.0f) * (sc - hgs);
+    const float X1 = (((float)rn_morton3d_invert(m >> 1) / gm1) * 2.0f - 1.0f) * (sc - hgs);
+    const float X2 = (((float)rn_morton3d_invert(m >> 2) / gm1) * 2.0f - 1.0f) * (sc - hgs);
+    int n_cov = 0;
+    bool near_hit = false;
+    for (int cam = 0; cam < a.n_cams; ++cam) {
+        const float* P = a.poses + (int64_t)cam * 12;
+        const float d0 = X0 - P[3], d1 = X1 - P[7], d2 = X2 - P[11];
+        const float xc = (P[0] * d0 + P[4] * d1) + P[8] * d2;
+        const float yc = (P[1] * d0 + P[5] * d1) + P[9] * d2;
+        const float zc = (P[2] * d0 + P[6] * d1) + P[10] * d2;
+        const float px = a.fx * xc + a.cx * zc;
+        const float py = a.fy * yc + a.cy * zc;
+        const bool in_image = zc > 0.f && px >= 0.f && px < a.w * zc && py >= 0.f && py < a.h * zc;
+        n_cov += (in_image && zc >= a.near) ? 1 : 0;
+        near_hit = near_hit || (in_image && zc < a.near);
+    }
+    a.count[e] = (float)n_cov / (float)a.n_cams;
+    const bool invalid = !(n_cov > 0 && !near_hit);
+    const unsigned long long bal = __ballot(invalid);
+    const int lane = rn_lane();
+    const uint32_t byte = (uint32_t)(bal >> (lane & 56)) & 0xffu;       // this lane's 8-cell byte
+    for (int k = 0; k < a.K; ++k) {
+        float* g = a.grids[k] + e;
+        const float d = *g;
+        *g = invalid ? -1.0f : (d < 0.f ? 0.0f : d);
+        if ((lane & 7) == 0 && byte) {
+            uint8_t* b = a.bitfields[k] + (e >> 3);
+            *b = (uint8_t)(*b & ~byte);
+        }
+    }
+    if (a.n_culled) {
+        __shared__ int sN;
+        if (threadIdx.x == 0) sN = 0;
+        __syncthreads();
+        if (lane == 0) atomicAdd(&sN, (int)__popcll(bal));
+        __syncthreads();
+        if (threadIdx.x == 0 && sN) atomicAdd(a.n_culled + c, sN);
+    }
+}
+
 inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
 
 }  // namespace
@@ -123,6 +191,32 @@ int rn_scatter_max(const int64_t* indices, const float* values, int64_t n, float
     if (n == 0) return 0;
     RN_CHECK_ARG(indices && values && out, "null pointer");
     k_scatter_max<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(n, indices, values, out);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_mark_invisible_cells(const float* poses, int32_t n_cams, float fx, float fy, float cx,
+                            float cy, int32_t width, int32_t height, float near_distance,
+                            const void* grid_ptrs, const void* bitfield_ptrs, int32_t n_models,
+                            int32_t cascades, int32_t grid_size, float scale, float* count_grid,
+                            int32_t* n_culled, void* stream) {
+    RN_CHECK_ARG(n_models >= 1 && cascades >= 1 && cascades <= 32 && grid_size == 128,
+                 "bad sizes (grid_size 128, cascades <= 32)");
+    RN_CHECK_ARG(n_cams >= 1 && width >= 1 && height >= 1, "needs a camera and a positive image size");
+    RN_CHECK_ARG(poses && grid_ptrs && bitfield_ptrs && count_grid, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_culled && hipMemsetAsync(n_culled, 0, sizeof(int32_t) * cascades, st) != hipSuccess) {
+        rn_set_error("%s: memset failed", __func__);
+        return 2;
+    }
+    MarkArgs a{};
+    a.poses = poses; a.grids = (float* const*)grid_ptrs; a.bitfields = (uint8_t* const*)bitfield_ptrs;
+    a.count = count_grid; a.n_culled = n_culled;
+    a.n_cams = n_cams; a.K = n_models; a.G = grid_size;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.w = (float)width; a.h = (float)height;
+    a.near = near_distance; a.scale = scale;
+    const int64_t n = (int64_t)cascades * grid_size * grid_size * grid_size;   // a multiple of 256
+    k_mark_invisible<<<(int)(n / 256), 256, 0, st>>>(a);
     RN_CHECK_LAUNCH();
     return 0;
 }

@@ -37,6 +37,8 @@ SIGNATURES = {
     "rn_set_level_pairing": [ctypes.c_uint64],
     "rn_density_update_sampled": [P, P, I32, I32, I32, F32, F32, F32, U64, P, P, P, P, P, P, P,
                                   P, P, P, P, P, P, I32, P],
+    "rn_density_update_visible": [P, P, I32, I32, I32, F32, F32, F32, U64, P, P, P, P, P, P, P,
+                                  P, P, P, P, P, P, I32, P, I32, P],
     "rn_distortion_loss_fw": [P, P, P, P, I64, P, P, P, P],
     "rn_distortion_loss_bw": [P, P, P, P, P, P, P, I64, P, P],
     "rn_raymarching_train_count": [P, P, P, P, I32, F32, F32, P, I32, I32, I64, P, P],
@@ -103,6 +105,8 @@ SIGNATURES = {
     "rn_morton3d_invert": [P, I64, P, P],
     "rn_packbits": [P, I64, F32, P, P],
     "rn_scatter_max": [P, P, I64, P, P],
+    "rn_mark_invisible_cells": [P, I32, F32, F32, F32, F32, I32, I32, F32, P, P, I32, I32, I32,
+                                F32, P, P, P],
 }
 
 ABI_VERSION = 9

@@ -325,15 +325,18 @@ def step_generator(device, seed, step):
     return g
 
 
-def update_density_grid(model, density_threshold, step, warmup=False, seed=0, decay=0.95):
+def update_density_grid(model, density_threshold, step, warmup=False, seed=0, decay=0.95,
+                        erode=False):
     """train_ml.py:174-177 (model.update_density_grid every update_interval
     steps) made rank-consistent: the warm-up's jitter comes from
     step_generator(seed, step), the sampled update's cells and jitter from the
-    device-side hash of the same (seed, step) -- identical on every rank."""
+    device-side hash of the same (seed, step) -- identical on every rank.
+    `erode` is passed through (it needs model.mark_invisible_cells first)."""
     if warmup:
         g = step_generator(model.mlp_params.device, seed, step)
-        model.update_density_grid(density_threshold, warmup=True, decay=decay, generator=g)
+        model.update_density_grid(density_threshold, warmup=True, decay=decay, erode=erode,
+                                  generator=g)
     else:
         # device-side draws from a hash of (seed, step): the same on every rank
-        model.update_density_grid(density_threshold, warmup=False, decay=decay,
+        model.update_density_grid(density_threshold, warmup=False, decay=decay, erode=erode,
                                   seed=(int(seed) * 1000003 + int(step)) & 0x7FFFFFFFFFFFFFFF)

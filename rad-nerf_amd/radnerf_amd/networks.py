@@ -29,6 +29,7 @@ from . import vren
 from ._lib import lib
 
 RGB_ACTS = ("Sigmoid",)
+NEAR_DISTANCE = 0.01        # rendering.NEAR_DISTANCE (ml_rendering.py:8)
 
 
 def _stream(dev):
@@ -369,19 +370,94 @@ class MNGP(nn.Module):
         seed it identically keep bit-identical grids and bitfields with no
         collective, radnerf_amd.dist) or from torch's default generator (as the
         reference's torch.randint / rand_like).  sigma comes from the density
-        kernel (hash grid + geo MLP, networks.py:393-394).  `erode` (off in
-        train_ml.py) is not supported."""
-        if erode:
-            raise NotImplementedError("update_density_grid(erode=True): not used by train_ml.py")
+        kernel (hash grid + geo MLP, networks.py:393-394).  After
+        mark_invisible_cells the update goes through rn_density_update_visible:
+        culled (negative) cells are neither drawn nor evaluated, and `erode`
+        (networks.py:396-398, off in train_ml.py) decays each cell by
+        clamp(decay ** (1 / count_grid), 0.1, 0.95); without a count_grid
+        `erode` raises ValueError."""
+        if erode and getattr(self, "count_grid", None) is None:
+            raise ValueError("update_density_grid(erode=True) needs the count_grid: call "
+                             "mark_invisible_cells(K, poses, img_wh) first")
         if seed is None:
             dev = generator.device if generator is not None else torch.device("cpu")
             seed = int(torch.randint(1 << 62, (1,), generator=generator, device=dev))
-        return self._update_sampled_device(density_threshold, decay, seed, all_cells=warmup)
+        return self._update_sampled_device(density_threshold, decay, seed, all_cells=warmup,
+                                           erode=erode)
+
+    def _grid_ptrs(self):
+        """Device array of the K density-grid pointers followed by the K
+        bitfield pointers (the grids made contiguous fp32 first)."""
+        K, C, G = self.size, self.cascades, self.grid_size
+        dev = self.mlp_params.device
+        grids = [getattr(self, f"density_grid_{i}") for i in range(K)]
+        bits = [getattr(self, f"density_bitfield_{i}") for i in range(K)]
+        for i, g in enumerate(grids):
+            if not (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == C * G ** 3):
+                g = g.float().contiguous()
+                setattr(self, f"density_grid_{i}", g)
+                grids[i] = g
+        return torch.tensor([g.data_ptr() for g in grids] + [b.data_ptr() for b in bits],
+                            dtype=torch.int64).to(dev, non_blocking=True)
 
     @torch.no_grad()
-    def _update_sampled_device(self, density_threshold, decay, seed, all_cells=False):
-        """The update of every sub-NeRF in one rn_density_update_sampled call;
-        the density grids and bitfields are updated in place."""
+    def mark_invisible_cells(self, K, poses, img_wh, near_distance=NEAR_DISTANCE):
+        """Cull the occupancy grids to the training cameras' frusta (upstream
+        ngp_pl's mark_invisible_cells, rn_mark_invisible_cells): a cell whose
+        centre no camera covers, or that some camera sees closer than
+        `near_distance`, becomes -1 in every sub-NeRF's density grid with its
+        bitfield bit cleared; the updates then skip it.  K: the 3x3 pinhole
+        intrinsics (tensor or array) shared by all cameras; poses: (N, 3, 4)
+        c2w fp32 on the model's device (axes right / down / front); img_wh:
+        (W, H).  Sets self.count_grid ((cascades, 128^3), the share of the
+        cameras covering each cell: a plain attribute, not part of the
+        state_dict) and returns the per-cascade culled counts (int32 device
+        tensor).  Idempotent; call it again after loading a checkpoint."""
+        Kh = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
+        if Kh.shape != (3, 3):
+            raise ValueError(f"mark_invisible_cells: K must be a 3x3 intrinsics matrix, got "
+                             f"shape {Kh.shape}")
+        if not torch.is_tensor(poses):
+            raise ValueError("mark_invisible_cells: poses must be a tensor")
+        if poses.ndim != 3 or tuple(poses.shape[1:]) != (3, 4):
+            raise ValueError(f"mark_invisible_cells: poses must be (N, 3, 4), got "
+                             f"{tuple(poses.shape)}")
+        if poses.shape[0] < 1:
+            raise ValueError("mark_invisible_cells: needs at least one camera")
+        if poses.dtype != torch.float32:
+            raise ValueError(f"mark_invisible_cells: poses must be float32, got {poses.dtype}")
+        dev = self.mlp_params.device
+        if poses.device != dev:
+            raise ValueError(f"mark_invisible_cells: poses are on {poses.device}, the model on "
+                             f"{dev}")
+        try:
+            W, H = (int(v) for v in img_wh)
+        except (TypeError, ValueError):
+            raise ValueError(f"mark_invisible_cells: img_wh must be (W, H), got {img_wh!r}")
+        if W < 1 or H < 1:
+            raise ValueError(f"mark_invisible_cells: img_wh must be positive, got {(W, H)}")
+        if dev.type != "cuda":
+            raise ValueError("mark_invisible_cells: the model must be on the GPU")
+        C, G = self.cascades, self.grid_size
+        poses = poses.contiguous()
+        count = torch.empty(C, G ** 3, device=dev)
+        culled = torch.empty(C, device=dev, dtype=torch.int32)
+        ptrs = self._grid_ptrs()
+        lib().mark_invisible_cells(
+            poses.data_ptr(), poses.shape[0], float(Kh[0, 0]), float(Kh[1, 1]), float(Kh[0, 2]),
+            float(Kh[1, 2]), W, H, float(near_distance), ptrs.data_ptr(),
+            ptrs.data_ptr() + 8 * self.size, self.size, C, G, float(self.scale),
+            count.data_ptr(), culled.data_ptr(), _stream(dev))
+        self._du_ptrs = ptrs          # keep the pointer array alive until the launch ran
+        self.count_grid = count
+        return culled
+
+    @torch.no_grad()
+    def _update_sampled_device(self, density_threshold, decay, seed, all_cells=False,
+                               erode=False):
+        """The update of every sub-NeRF in one rn_density_update_sampled call
+        (rn_density_update_visible once a count_grid exists); the density grids
+        and bitfields are updated in place."""
         K, C, G = self.size, self.cascades, self.grid_size
         dev = self.mlp_params.device
         n = K * C * G ** 3
@@ -394,23 +470,22 @@ class MNGP(nn.Module):
                   "part": torch.empty(K * 1024, device=dev),
                   "thr": torch.empty(K, device=dev)}
             self._du = du
-        grids = [getattr(self, f"density_grid_{i}") for i in range(K)]
-        bits = [getattr(self, f"density_bitfield_{i}") for i in range(K)]
-        for i, g in enumerate(grids):
-            if not (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == C * G ** 3):
-                g = g.float().contiguous()
-                setattr(self, f"density_grid_{i}", g)
-                grids[i] = g
-        ptrs = torch.tensor([g.data_ptr() for g in grids] + [b.data_ptr() for b in bits],
-                            dtype=torch.int64).to(dev, non_blocking=True)
+        ptrs = self._grid_ptrs()
         lo, lh, lr, ls = self.xyz_encoder.level_ptrs()
-        lib().density_update_sampled(
-            ptrs.data_ptr(), ptrs.data_ptr() + 8 * K, K, C, G, float(self.scale),
-            float(density_threshold), float(decay), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            self.xyz_encoder.params_f16().data_ptr(), lo, lh, lr, ls, self._h_min.ctypes.data,
-            self._h_ext.ctypes.data, self.packed_frags().data_ptr(), du["tmp"].data_ptr(),
-            du["occ"].data_ptr(), du["blk"].data_ptr(), du["part"].data_ptr(),
-            du["thr"].data_ptr(), int(bool(all_cells)), _stream(dev))
+        args = (ptrs.data_ptr(), ptrs.data_ptr() + 8 * K, K, C, G, float(self.scale),
+                float(density_threshold), float(decay), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                self.xyz_encoder.params_f16().data_ptr(), lo, lh, lr, ls, self._h_min.ctypes.data,
+                self._h_ext.ctypes.data, self.packed_frags().data_ptr(), du["tmp"].data_ptr(),
+                du["occ"].data_ptr(), du["blk"].data_ptr(), du["part"].data_ptr(),
+                du["thr"].data_ptr(), int(bool(all_cells)))
+        count = getattr(self, "count_grid", None)
+        if count is None:
+            lib().density_update_sampled(*args, _stream(dev))
+        else:
+            if count.device != dev or tuple(count.shape) != (C, G ** 3):
+                raise ValueError("update_density_grid: count_grid does not match the grids; call "
+                                 "mark_invisible_cells again")
+            lib().density_update_visible(*args, count.data_ptr(), int(bool(erode)), _stream(dev))
         self._du_ptrs = ptrs          # keep the pointer array alive until the launch ran
         return du
 
@@ -431,6 +506,7 @@ class MNGP(nn.Module):
                                 device=dev))
             setattr(self, f"density_grid_{i}",
                     torch.zeros(self.cascades, self.grid_size ** 3, device=dev))
+        self.count_grid = None        # the cull belonged to the old box
         self._set_box_host()
 
     def _apply(self, fn, *args, **kwargs):

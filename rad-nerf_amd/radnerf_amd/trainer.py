@@ -50,6 +50,18 @@ schedules only net_opt), accumulates the epoch's loss terms on the device,
 reads them once per epoch for the log, and validates every `val_every` epochs
 and after the last.
 
+With the camera intrinsics the trainer culls the occupancy grids to the
+training cameras' frusta once, before the first step (upstream ngp_pl's
+mark_invisible_cells; MNGP.mark_invisible_cells), and the grid updates then
+skip the culled cells; `erode` decays cells seen by few cameras faster
+(networks.py:396-398):
+
+    tr = Trainer(model, gate, n_rays=8192, directions=directions, poses=poses,
+                 img_wh=(W, H), intrinsics=K, cull_invisible=True, erode=True)
+
+The cull uses the initial poses.  Under optimize_ext it is not repeated: the
+corrections move at lr 1e-8 and do not shift a frustum by a grid cell.
+
 Out of scope: dataset file readers, the Lightning loop,
 logging back-ends.
 """
@@ -75,7 +87,8 @@ class Trainer:
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
-                 optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None):
+                 optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None, intrinsics=None,
+                 cull_invisible=False, erode=False):
         if optimize_ext and (directions is None or poses is None):
             raise ValueError("Trainer(optimize_ext=True) needs directions (P, 3) and poses "
                              "(N, 3, 4): the pose corrections are per image of `poses`")
@@ -88,6 +101,14 @@ class Trainer:
             if len(img_wh) != 2 or int(img_wh[0]) * int(img_wh[1]) != directions.shape[0]:
                 raise ValueError(f"Trainer: img_wh {tuple(img_wh)} does not match the "
                                  f"{directions.shape[0]} rows of directions")
+        if cull_invisible and (intrinsics is None or poses is None or img_wh is None):
+            raise ValueError("Trainer(cull_invisible=True) needs intrinsics (3x3), poses "
+                             "(N, 3, 4) and img_wh (W, H): the cells are tested against "
+                             "those cameras' frusta")
+        if erode and not cull_invisible and getattr(model, "count_grid", None) is None:
+            raise ValueError("Trainer(erode=True) needs cull_invisible=True (or a model "
+                             "already marked by mark_invisible_cells): the erode decay "
+                             "divides by the count_grid")
         if images is not None:
             from .sampler import TrainImages
             if directions is None:
@@ -153,6 +174,12 @@ class Trainer:
         # reduce_and_step); False: one collective, a division, then Adam
         self.bucketed = bucketed
         self.global_step = 0
+        # the grid updates' erode decay, and the one-off frustum cull (from the
+        # initial poses: dR / dT at lr 1e-8 do not move a frustum by a cell)
+        self.erode = bool(erode)
+        self.n_culled = None
+        if cull_invisible:
+            self.n_culled = model.mark_invisible_cells(intrinsics, self.poses, self.img_wh)
 
     def _bg(self):
         """ml_rendering.py:192-198"""
@@ -216,7 +243,7 @@ class Trainer:
             rdist.update_density_grid(self.model, 0.01 * MAX_SAMPLES / 3 ** 0.5,
                                       self.global_step,
                                       warmup=self.global_step < self.warmup_steps,
-                                      seed=self.seed)
+                                      seed=self.seed, erode=self.erode)
         B, K = rays_o.shape[0], self.model.size
         if noise is None:
             noise = torch.rand(K, B, device=self.device)
