@@ -699,6 +699,41 @@ int rn_image_sse(const float* pred, const float* target, int64_t n_elems, void* 
 int rn_ssim(const float* pred, const float* target, int32_t H, int32_t W, int32_t C, void* work,
             double* out_sum, float* ssim_map /*may be NULL*/, void* stream);
 
+/* ---- validation images (train_ml.py:47-52,238-248) --------------------------
+ * The 8-bit pictures validation_step saves: (rgb * 255).astype(uint8), the
+ * gate-weighted depth through depth2img (min-max normalise, COLORMAP_TURBO),
+ * and a picture of the per-ray gating code.  All arithmetic is fp32, every
+ * operation rounded on its own.  n == 0 is a valid no-op for all four; invalid
+ * arguments give status 1 and nothing is written.  fp32 pointers must be
+ * 4-byte aligned; uint8 pointers need no alignment (aligned dense buffers take
+ * 16-byte loads, the rest dword loads; the result is the same).
+ * rn_minmax_finite: out2 (two device floats) = {min, max} of x[i * stride],
+ * i < n, over the finite values only (NaN, +-inf skipped); {0, 0} when there
+ * is none (also n == 0).  stride >= 1 in elements, so one column of an (N, K)
+ * buffer is read in place.  Per-block partials, then one fixed-order pass, no
+ * atomics.  work: RN_METRICS_WORK_BYTES, as the metrics above.
+ * rn_quantize_u8: dst[i] = src[i] * 255.0f, NaN -> 0, clamped to [0, 255],
+ * truncated toward zero: numpy's astype(uint8) wherever that is defined.
+ * rn_colormap_u8: depth2img.  range2 = {mn, mx} is read on the device (what
+ * rn_minmax_finite wrote: no host round trip); den = mx - mn.  The index is 0
+ * if !(den > 0) or x is not finite; else t = (x - mn) / den (a division),
+ * t * 255.0f, NaN -> 0, clamped to [0, 255], truncated.  dst (n, 3) =
+ * lut[index]; lut is 256 x 3 uint8 on the device; swap_rb != 0 exchanges
+ * channels 0 and 2 of the output (the reference saves cv2's BGR as it is).
+ * rn_gate_map_u8: gate (n, n_models) row-major, 1 <= n_models <= 16 (as
+ * rn_gate_fwd); palette (n_models, 3) uint8 on the device; dst (n, 3).
+ * hard == 0, per channel c: acc = g[0] * (float)p[0][c], then acc = acc +
+ * g[k] * (float)p[k][c], k ascending; the byte is acc + 0.5f, NaN -> 0,
+ * clamped to [0, 255], truncated.  hard != 0: the palette row of the first
+ * maximal gate; a NaN never wins, row 0 if every gate is NaN.                */
+int rn_minmax_finite(const float* x, int64_t n, int64_t stride, void* work, float* out2,
+                     void* stream);
+int rn_quantize_u8(const float* src, int64_t n, uint8_t* dst, void* stream);
+int rn_colormap_u8(const float* x, int64_t n, int64_t stride, const float* range2,
+                   const uint8_t* lut, int32_t swap_rb, uint8_t* dst, void* stream);
+int rn_gate_map_u8(const float* gate, int64_t n, int32_t n_models, const uint8_t* palette,
+                   int32_t hard, uint8_t* dst, void* stream);
+
 /* ---- parameter packing (f32 master -> f16 MFMA fragments / f16 grid) ------*/
 int rn_pack_f16(const float* src, int64_t src_stride, const int32_t* index, int64_t n,
                 int32_t n_models, int64_t dst_stride, void* dst, void* stream);

@@ -10,6 +10,7 @@ this package is the Python host side mirroring the reference's interfaces:
   dist               ray-batch data parallelism over RCCL
   evaluate           whole-image validation render (ImageEvaluator)
   metrics            PSNR / SSIM of validation_step on the device
+  imageout           8-bit rgb / depth2img / gate map on the device, PNG files
   sampler            a training step's inputs from device-resident images
                      (TrainImages / sample_batch), the cosine lr schedule
 """

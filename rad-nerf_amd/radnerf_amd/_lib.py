@@ -99,6 +99,10 @@ SIGNATURES = {
     "rn_ml_combine_test": [P, P, P, P, P, I64, I32, I64, P, P, P, P, P],
     "rn_image_sse": [P, P, I64, P, P, P],
     "rn_ssim": [P, P, I32, I32, I32, P, P, P, P],
+    "rn_minmax_finite": [P, I64, I64, P, P, P],
+    "rn_quantize_u8": [P, I64, P, P],
+    "rn_colormap_u8": [P, I64, I64, P, P, I32, P, P],
+    "rn_gate_map_u8": [P, I64, I32, P, I32, P, P],
     "rn_pack_f16": [P, I64, P, I64, I32, I64, P, P],
     "rn_to_f16": [P, I64, P, P],
     "rn_morton3d": [P, I64, P, P],

@@ -6,6 +6,7 @@ SSIM against the ground truth out.
     res = ev.render_image(pose)          # rgb (H*W,3), opacity, depth, depth_k,
                                          # gating_code (H*W,K), total_samples
     m = ev.evaluate(pose, rgb_gt)        # {"psnr", "ssim"} device scalars
+    im = ev.images8()                    # uint8 (H, W, 3): rgb, depth, gate (K > 1)
 
 Per chunk of rays: rn_get_rays (one pose, the chunk's directions by pointer
 offset) -> the gate (rn_gate_fwd on rays_o / rays_d in place, written into
@@ -18,7 +19,7 @@ the current stream with no host synchronisation and no per-chunk allocation.
 """
 import torch
 
-from . import metrics
+from . import imageout, metrics
 from ._lib import lib
 from .rendering import MAX_SAMPLES, NEAR_DISTANCE
 
@@ -98,6 +99,7 @@ class ImageEvaluator:
                     "gating_code": torch.ones(N, K, **f32)}
         # ml_rendering.py:149-153: white beyond the samples unless exp stepping
         self.bg = torch.ones(3, **f32) if self.esf == 0 else torch.zeros(3, **f32)
+        self.out8 = None                                 # images8()'s buffers, on first use
 
     def _bitfields(self):
         """[K][bytes] contiguous, as rn_render_test reads them (refreshed per
@@ -176,3 +178,24 @@ class ImageEvaluator:
         _check_pose("ImageEvaluator.evaluate", pose)
         rgb = self.render_image(pose, T_threshold, max_samples)["rgb"]
         return {"psnr": metrics.psnr(rgb, rgb_gt), "ssim": metrics.ssim(rgb, rgb_gt, self.img_wh)}
+
+    def images8(self, swap_rb=False, hard_gate=False):
+        """The pictures validation_step saves (train_ml.py:238-248), from the
+        buffers the last render_image filled: device uint8 (H, W, 3) tensors
+        "rgb" ((rgb * 255).astype(uint8)), "depth" (depth2img of the
+        gate-weighted depth, train_ml.py:243; swap_rb: red and blue exchanged,
+        as the reference's files) and, for K > 1, "gate" (imageout.gate2img of
+        the gating code, default palette; hard_gate: the first maximal gate's
+        colour).  The buffers are the evaluator's own, reused by the next call;
+        nothing synchronises with the host."""
+        W, H = self.img_wh
+        K = self.model.size
+        if self.out8 is None:
+            self.out8 = {k: torch.empty(H, W, 3, dtype=torch.uint8, device=self.device)
+                         for k in (("rgb", "depth", "gate") if K > 1 else ("rgb", "depth"))}
+        out, out8 = self.out, self.out8
+        imageout.to_uint8(out["rgb"], out=out8["rgb"])
+        imageout.depth2img(out["depth"], swap_rb=swap_rb, out=out8["depth"])
+        if K > 1:
+            imageout.gate2img(out["gating_code"], hard=hard_gate, out=out8["gate"])
+        return dict(out8)

@@ -83,6 +83,9 @@ def _rank():
 
 
 class Trainer:
+    # fit(): where its validations write their images (validate's save_dir); None: nowhere
+    val_save_dir = None
+
     def __init__(self, model, gating_net, n_rays, lr=1e-2, lambda_opacity=1e-3,
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
@@ -277,7 +280,8 @@ class Trainer:
         self.global_step += 1
         return terms
 
-    def validate(self, poses, images, T_threshold=1e-4):
+    def validate(self, poses, images, T_threshold=1e-4, save_dir=None, epoch=0, swap_rb=False,
+                 hard_gate=False):
         """validation_step (train_ml.py:214-250) over (pose, image) pairs:
         poses (N, 3, 4) camera-to-world, used as they are (the test split's own
         poses: no dR / dT, as the reference), images (N, H*W, 3) fp32 (or a
@@ -285,7 +289,13 @@ class Trainer:
         "ssim": mean, "per_image": [{"psnr", "ssim"}, ...]}, device fp64
         scalars, with no host synchronisation.  Training state is untouched:
         no density-grid update, no step.  Each rank evaluates what it is
-        given."""
+        given.
+        save_dir: also write image i as `{i:03d}epoch{epoch}.png`, its
+        gate-weighted depth as `..._d.png` (train_ml.py:238-248; swap_rb: red
+        and blue exchanged, as the reference's files) and, with more than one
+        sub-NeRF, the gate map as `..._g.png` (ImageEvaluator.images8,
+        imageout.ImageSaver); the files are complete on return, the numbers
+        are the same.  Without it nothing more is launched or allocated."""
         from .evaluate import ImageEvaluator
         from .metrics import ImageMetrics
         if self.directions is None or self.img_wh is None:
@@ -309,11 +319,22 @@ class Trainer:
         if self._evaluator is None:
             self._evaluator = ImageEvaluator(self.model, self.gate, self.directions, self.img_wh,
                                              exp_step_factor=self.esf)
+        saver = None
+        if save_dir is not None:
+            from .imageout import ImageSaver
+            saver = ImageSaver(save_dir)
         acc = ImageMetrics()
-        for pose, im in zip(poses, images):
+        for i, (pose, im) in enumerate(zip(poses, images)):
             im = im.to(self.device)
             rgb = self._evaluator.render_image(pose, T_threshold)["rgb"]
             acc.update(rgb, im, self.img_wh)
+            if saver is not None:
+                im8 = self._evaluator.images8(swap_rb=swap_rb, hard_gate=hard_gate)
+                for kind, tail in (("rgb", ""), ("depth", "_d"), ("gate", "_g")):
+                    if kind in im8:
+                        saver.save(f"{i:03d}epoch{int(epoch)}{tail}.png", im8[kind], kind)
+        if saver is not None:
+            saver.flush()
         return acc.compute()
 
     def fit(self, num_epochs=30, steps_per_epoch=1000, val_poses=None, val_images=None,
@@ -331,6 +352,9 @@ class Trainer:
         train_psnr (-10 log10 of the epoch's mean rgb MSE, what the accumulated
         PeakSignalNoiseRatio(data_range=1) logs) and, where it ran, val
         {"psnr", "ssim"} as floats.  callback(entry) is called once per epoch.
+        With `val_save_dir` set on the trainer (None by default) each
+        validation also writes its images there, named by the epoch (validate's
+        save_dir and epoch).
         The batches depend on (seed, global_step, rank) alone: a trainer
         resumed with the same seed and global_step continues the stream."""
         from .sampler import cosine_lr
@@ -367,7 +391,8 @@ class Trainer:
                      else math.inf}
             if val_poses is not None and ((epoch + 1) % val_every == 0
                                           or epoch == num_epochs - 1):
-                val = self.validate(val_poses, val_images)
+                val = self.validate(val_poses, val_images, save_dir=self.val_save_dir,
+                                    epoch=epoch)
                 entry["val"] = {k: float(val[k]) for k in ("psnr", "ssim")}
             log.append(entry)
             if callback is not None:
