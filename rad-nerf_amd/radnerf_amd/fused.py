@@ -375,6 +375,23 @@ class FusedMLRenderer:
         self.trace = False
         self.events = {}
 
+    @property
+    def scatter_mode(self):
+        """How the next backward accumulates the grid gradient, from the
+        switches as they stand: "binned" (page records, bin + sum passes),
+        "fixed-point" (int32 atomics + fold), "int-grad" (exact u32 atomics
+        with carries) or "fp32-atomics".  grid_fx / grid_bin / int_grad only
+        act in the merged backward (_field): the per-model backward
+        (merged_bwd off, the default above 8 sub-NeRFs) always scatters with
+        fp32 atomics, whatever they say."""
+        if not self.merged_bwd:
+            return "fp32-atomics"
+        if self.int_grad:
+            return "int-grad"
+        if self.grid_fx and self.feat_cache:
+            return "binned" if self.grid_bin else "fixed-point"
+        return "fp32-atomics"
+
     def _ev(self, name, L_call, *args, stream=None):
         """Launch through librn; with tracing on (for this kernel), bracket it
         with events on the launch stream (bench.py's per-kernel timing)."""
@@ -692,6 +709,12 @@ class FusedMLRenderer:
             self._ev("field_bwd", L.field_bwd, *common, w.dsigma.data_ptr(),
                      w.drgb.data_ptr(), grid_grad.data_ptr(), dw.data_ptr(),
                      w.feat.data_ptr() if self.feat_cache else None, self.bwd_blocks, st)
+            # per-model backward: fp32 atomics only, so the MLP gradient and the
+            # whole grid gradient are final after this one launch
+            if self.after_field_bwd is not None:
+                self.after_field_bwd()
+            if self.after_grid_levels is not None:
+                self.after_grid_levels(0)
 
     # pool growth reads the page count of the binned backward this many
     # backwards back, waiting for it if needed (reading whichever

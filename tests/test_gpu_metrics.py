@@ -114,7 +114,7 @@ def _combine_ref(gate, op_k, depth_k, rgb_k, bg):
 
 
 @pytest.mark.parametrize("B", [1, 63, 257])
-@pytest.mark.parametrize("K", [1, 2, 4])
+@pytest.mark.parametrize("K", [1, 2, 4, 9, 16])
 def test_ml_combine_test_vs_torch(cuda, K, B):
     g = torch.Generator().manual_seed(100 * K + B)
     gate = torch.softmax(torch.randn(B, K, generator=g), 1).to(cuda).contiguous()

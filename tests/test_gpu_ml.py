@@ -187,11 +187,13 @@ def test_workspace_reuse_is_caught(cuda):
         torch.autograd.backward([res["rgb"]], [to(seeds[0])])
 
 
-@pytest.mark.parametrize("B,K,scale", [(1001, 2, 0.5), (777, 5, 0.5), (333, 8, 16.0)])
+@pytest.mark.parametrize("B,K,scale", [(1001, 2, 0.5), (777, 5, 0.5), (333, 8, 16.0),
+                                       (72, 12, 0.5)])
 def test_fused_vs_dropin_ragged(cuda, B, K, scale):
     """Ragged batch sizes and K = 5 / 8 (merged forward with the MLP
     fragments in global memory, generic plan): the fused chain against the
-    reference-structured drop-in chain, outputs and gradients."""
+    reference-structured drop-in chain, outputs and gradients.  K = 12: the
+    per-model field kernels (no merged kernel above 8 sub-NeRFs)."""
     esf = 1 / 256 if scale > 0.5 else 0.0
     m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
     rf, gf = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, esf)

@@ -78,3 +78,32 @@ def test_chunk_defaults_by_shape():
                             capacity=1024)
         assert (r.head_chunk, r.min_chunk) == (head, mn), (scale, K, B, r.head_chunk, r.min_chunk)
         assert r.head_chunk <= r.max_chunk        # (the plan takes min(min_chunk, max_chunk))
+
+
+def test_many_models_defaults_and_scatter_mode():
+    """Above 8 sub-NeRFs the merged kernels do not apply (rn_field_bwd_merged /
+    rn_field_fwd_merged / rn_field_fwd_levels: K <= 8): the default renderer
+    runs the per-model forward and backward, whose grid scatter is fp32
+    atomics whatever grid_fx / grid_bin say (they are still set by shape), so
+    scatter_mode -- what a run reports -- says fp32 there, and names the
+    merged backward's mode at K <= 8."""
+    import torch
+    from radnerf_amd.fused import FusedMLRenderer
+    cpu = torch.device("cpu")
+    for K in (9, 16):
+        for scale in (0.5, 16.0):
+            r = FusedMLRenderer(MNGP(scale, size=K, seed=3), Ray_Gate(K, seed=4), 1024, device=cpu,
+                                capacity=1024)
+            assert (r.merged_bwd, r.merged_fwd, r.level_fwd) == (False, False, False), (K, scale)
+            assert (r.fwd_blocks, r.bwd_blocks) == (2048 // K, 256 // K)
+            assert r.grid_fx and r.grid_bin == (scale > 0.5)        # set, but unused here
+            assert r.scatter_mode == "fp32-atomics", (K, scale, r.scatter_mode)
+    for scale, K, B, want in ((16.0, 8, 1024, "binned"), (0.5, 2, 8192, "fixed-point"),
+                              (0.5, 1, 1024, "fp32-atomics"), (16.0, 1, 512, "fp32-atomics")):
+        r = FusedMLRenderer(MNGP(scale, size=K, seed=3), Ray_Gate(K, seed=4), B, device=cpu,
+                            capacity=1024)
+        assert r.merged_bwd and r.scatter_mode == want, (scale, K, B, r.scatter_mode)
+        r.merged_bwd = False
+        assert r.scatter_mode == "fp32-atomics"
+        r.merged_bwd, r.int_grad = True, True
+        assert r.scatter_mode == "int-grad"

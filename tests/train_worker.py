@@ -62,7 +62,7 @@ def main(out_path, scale=0.5):
         res = {"world": world, "identical": {k: all(a[k] == mine[k] for a in allr) for k in mine},
                "bitfields_changed": changed, "occupancy_byte_mean": occ, "losses": losses,
                "finite": bool(all(torch.isfinite(v.float()).all() for v in state.values())),
-               "grid_bin": bool(tr.renderer.grid_bin and tr.renderer.grid_fx),
+               "grid_bin": tr.renderer.scatter_mode == "binned",
                "bin_pages": (int(tr.renderer.ws._bin["ctl"][0])
                              if getattr(tr.renderer.ws, "_bin", None) else 0)}
         with open(out_path, "w") as f:
