@@ -67,12 +67,13 @@ def test_field_forward(cuda, scale):
         assert e_sig.max() <= 1e-2, e_sig.max()
 
 
-@pytest.mark.parametrize("zero_span", [None, (600, 3100)])
-def test_field_backward(cuda, zero_span):
+@pytest.mark.parametrize("zero_span,scale", [
+    pytest.param(None, 0.5, id="None"), pytest.param((600, 3100), 0.5, id="zero_span1"),
+    pytest.param(None, 16.0, id="None-16.0"), pytest.param((600, 3100), 16.0, id="zero_span1-16.0")])
+def test_field_backward(cuda, zero_span, scale):
     """zero_span: samples whose seeds are zero (as past a ray's early
     termination); covers whole 256-sample backward iterations, which the
-    kernel skips, and partial ones."""
-    scale = 0.5
+    kernel skips, and partial ones.  scale 16: 4 dense levels instead of 6."""
     m = _model(cuda, scale)
     n = 4000
     x, d = _inputs(n, scale, seed=4)
@@ -98,7 +99,7 @@ def test_field_backward(cuda, zero_span):
     # random points with N(0, 1) seeds: the f16 chain's relative error is
     # larger than on rendered samples (no composite weighting)
     check_grads(scale, g_grid, gp.grad.numpy(), g_mlp[ind], mp.grad[ind].numpy(),
-                tag=f"field zero_span={zero_span}", grid_tol=FIELD_GRID_TOL, mlp_tol=FIELD_MLP_TOL)
+                tag=f"field scale {scale} zero_span={zero_span}", grid_tol=FIELD_GRID_TOL, mlp_tol=FIELD_MLP_TOL)
     assert np.abs(g_mlp[1 - ind]).max() == 0
 
 
