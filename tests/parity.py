@@ -3,7 +3,15 @@ hash-grid level (16) and per MLP layer of every sub-NeRF (g1 g2 r1 r2 r3),
 each against the fp32 oracle.  The bounds are about 2x the largest value
 measured on the test workloads (printed by every test that uses them; see
 DESIGN.md §2).  Whole-tensor norms could hide a dropped corner or a wrong fine
-level; these cannot."""
+level; these cannot.
+
+The composite kernels have per-sample bars of their own, derived instead of
+measured (tests/composite_ref.py, test_gpu_composite.py): against fp64, ws
+(k + 2) eps w, opacity / depth / rgb (m + 2) eps value, drgb (k + 3) eps |g w|,
+dsigma and the distortion loss and gradient (m + 16) eps sum|terms|, eps = 2^-24,
+exact zeros.  Kernel error / bound measured on the MI355X: ws 0.26, opacity
+0.17, depth 0.26, rgb 0.17, drgb 0.36, dsigma 0.096, distortion loss 0.032,
+its dL_dws 0.027, test-time step 0.42."""
 import numpy as np
 
 from radnerf_amd import layout as LY
