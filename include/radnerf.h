@@ -587,6 +587,69 @@ int rn_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq
             double lr, double beta1, double beta2, double eps, int32_t step, float grad_scale,
             void* params_f16, int64_t n_f16, void* stream);
 
+/* ---- deterministic training (opt-in; DESIGN.md §4 "Deterministic training") --
+ * Five entries that replace the step's four fp32 sums in arrival order, so the
+ * same parameters, inputs and seed give the same bits on one GPU in one
+ * process, however the blocks and waves happen to be scheduled.
+ * rn_reduce_partials: out[i] = (...((out[i] + part[0][i]) + part[1][i]) + ...
+ * + part[n_slots - 1][i]) for i in [0, n); part is [n_slots][n] fp32.  ORDER
+ * CONTRACT: plain fp32 adds in ascending slot order starting from the
+ * incoming out[i], one thread per i, no atomics, no tree: the result equals
+ * that loop bit for bit.  n_slots >= 1, n >= 0 (n == 0: nothing to do).
+ * rn_colsum_ordered: out[c] = sum over rows of x[r][c] (x (rows, cols) fp32,
+ * cols in 1..16; out written, not accumulated), gate.sum(0) without atomics.
+ * The summation tree depends on (rows, cols) alone: tile t of 32 rows is
+ * summed row by row (ascending) per column, then the tile sums are added in
+ * ascending t, each as ((s_t0 + s_t1) + ...) per lane over tiles t = lane, lane
+ * + 64, ..., then the 64 lane sums by a fixed xor butterfly (32, 16, ..., 1).
+ * rows == 0 writes zeros.
+ * rn_field_bwd_merged_det: rn_field_bwd_merged in the integer-grid form
+ * (igrad_lo / igrad_carry / igrad_scale required, see rn_seed_scale) without
+ * the fx_* / gb_* arguments.  SCHEDULE CONTRACT: chunk c of rn_bwd_plan's
+ * plan is processed by block c mod blocks, and each block takes its chunks in
+ * ascending c (queue is only read: [1], the chunk count; no ticket is taken),
+ * so what a block sums depends on the plan alone.  dw is replaced by dw_part
+ * ([blocks][n_models][9472] fp32): the entry zeroes it on the stream, then
+ * block b stores its dW into slot b, every parameter written by exactly one
+ * wave, once; a slot (or a model's row) of a block that met no sample of it
+ * stays zero.  Sum the slots with rn_reduce_partials(dw_part, blocks,
+ * n_models * 9472, dw).  The grid gradient goes to igrad_lo / igrad_carry
+ * (exact integer sums, order-free; rn_igrad_to_f32 folds them).
+ * rn_gate_bwd_det: rn_gate_bwd's results up to fp32 summation order, with one
+ * wave per block (64 threads; tile t of 32 rays goes to block t mod n_blocks):
+ * a block's adds run in its wave's program order, and the block stores its
+ * whole dW (zeros included) into slot b of gate_part ([n_blocks][n_params]
+ * fp32).  Sum with rn_reduce_partials(gate_part, n_blocks, n_params, dw).
+ * rn_nerf_loss_det: rn_nerf_loss with the three per-ray sums (loss_out [0],
+ * [1], [3]) written as per-block partials into part ([ceil(n_rays / 256)][4]
+ * fp32; each block's sum is a fixed xor butterfly per wave, then its four
+ * waves in order) and added in block order by one thread per term; loss_out
+ * [2] and the four seeds are rn_nerf_loss's, bit for bit.                   */
+int rn_reduce_partials(const float* part, int32_t n_slots, int64_t n, float* out, void* stream);
+int rn_colsum_ordered(const float* x, int64_t rows, int32_t cols, float* out, void* stream);
+int rn_field_bwd_merged_det(const float* ts, const int32_t* ray_of, const float* rays_o,
+                            const float* rays_d, const int32_t* seg_base,
+                            const int32_t* seg_count, const int32_t* mstart, const int32_t* perm,
+                            const int32_t* chunk_desc, const int32_t* queue, int64_t n_rays,
+                            int32_t n_models, int32_t max_samples, const void* grid_f16,
+                            const uint32_t* level_offset, const uint32_t* level_hsize,
+                            const uint32_t* level_res, const float* level_scale,
+                            const float* xyz_min, const float* extent, const void* frags,
+                            const float* dL_dsigma, const float* dL_drgb, float* grid_grad,
+                            float* dw_part, const void* feat_cache, float* scratch,
+                            int64_t scratch_rows, float* park, int32_t max_chunk, int32_t blocks,
+                            int32_t* igrad_lo, int32_t* igrad_carry, const float* igrad_scale,
+                            void* stream);
+int rn_gate_bwd_det(const float* in0, const float* in1, int32_t stride, int64_t n_rays,
+                    int32_t n_models, const void* frags, const float* dL_dgate, float* gate_part,
+                    int32_t n_params, const void* dinput_frags, float* dL_dinput,
+                    int32_t n_blocks, void* stream);
+int rn_nerf_loss_det(const float* rgb, const float* target_rgb, const float* opacity,
+                     const float* depth, const float* gate, const float* importance,
+                     int64_t n_rays, int32_t n_models, float lambda_opacity, float lambda_cv,
+                     float lambda_dm, float* loss_out, float* part, float* dL_drgb,
+                     float* dL_dopacity, float* dL_ddepth, float* dL_dgate, void* stream);
+
 /* rn_get_rays: train_ml.py:84-96 + ray_utils.py:45-70 for a batch of picks.
  * directions (P,3) camera-space; poses (I,3,4) c2w; img_idxs (n) or NULL
  * (one pose); pix_idxs (n) or NULL (directions are per ray).  imgs_d (n,3)

@@ -803,7 +803,8 @@ __device__ __forceinline__ f32x16 dw_block_tile(const rn_half* sImg, int ya, int
 }
 
 // flush one owned dW tile (accumulated at scale `sc`) into the global gradient
-template <int MODE>
+// (STORE: plain stores into the block's own slot, deterministic mode)
+template <int MODE, bool STORE = false>
 __device__ __forceinline__ void dw_flush(const f32x16& acc, float* dw, int off, int ncols,
                                          int out_base, int in_base, float inv) {
     const int lane = rn_lane(), col = lane & 31, h = lane >> 5;
@@ -814,7 +815,10 @@ __device__ __forceinline__ void dw_flush(const f32x16& acc, float* dw, int off, 
         if (MODE == DW_PLAIN) out = out_base + row;
         else if (MODE == DW_ROWS_LT3) out = row < 3 ? row : -1;
         else out = row < 16 ? row + 1 : (row == 16 ? 0 : -1);
-        if (out >= 0) atomicAdd(dw + off + out * ncols + in_base + col, acc[i] * inv);
+        if (out >= 0) {
+            if (STORE) dw[off + out * ncols + in_base + col] = acc[i] * inv;
+            else atomicAdd(dw + off + out * ncols + in_base + col, acc[i] * inv);
+        }
     }
 }
 
@@ -823,19 +827,20 @@ __device__ __forceinline__ void dw_flush(const f32x16& acc, float* dw, int off, 
 // (at the geo chain's scale); a zero scale means "empty"
 struct DwScale { float a, b; };
 
+template <bool STORE = false>
 __device__ __forceinline__ void dw_flush_owned(const f32x16& accA, const f32x16& accB, float* dw,
                                                int wid, DwScale sc) {
     const float ia = sc.a != 0.f ? 1.0f / sc.a : 0.f, ib = sc.b != 0.f ? 1.0f / sc.b : 0.f;
     if (wid < 2) {
-        if (ia != 0.f) dw_flush<DW_ROWS_LT3>(accA, dw, 9280, 64, 0, 32 * wid, ia);   // rgb3
-        if (ib != 0.f) dw_flush<DW_GEO>(accB, dw, 2048, 64, 0, 32 * wid, ib);        // geo2
+        if (ia != 0.f) dw_flush<DW_ROWS_LT3, STORE>(accA, dw, 9280, 64, 0, 32 * wid, ia);   // rgb3
+        if (ib != 0.f) dw_flush<DW_GEO, STORE>(accB, dw, 2048, 64, 0, 32 * wid, ib);        // geo2
     } else if (wid < 6) {
         const int mm = (wid - 2) >> 1, nn = (wid - 2) & 1;
-        if (ia != 0.f) dw_flush<DW_PLAIN>(accA, dw, 5184, 64, 32 * mm, 32 * nn, ia); // rgb2
+        if (ia != 0.f) dw_flush<DW_PLAIN, STORE>(accA, dw, 5184, 64, 32 * mm, 32 * nn, ia); // rgb2
         if (wid < 4 && ib != 0.f)
-            dw_flush<DW_PLAIN>(accB, dw, 0, 32, 32 * (wid - 2), 0, ib);              // geo1
+            dw_flush<DW_PLAIN, STORE>(accB, dw, 0, 32, 32 * (wid - 2), 0, ib);              // geo1
     } else {
-        if (ia != 0.f) dw_flush<DW_PLAIN>(accA, dw, 3136, 32, 32 * (wid - 6), 0, ia); // rgb1
+        if (ia != 0.f) dw_flush<DW_PLAIN, STORE>(accA, dw, 3136, 32, 32 * (wid - 6), 0, ia); // rgb1
     }
 }
 
@@ -1146,7 +1151,14 @@ __device__ __forceinline__ void dw_unpark(const float* p, f32x16& A, f32x16& B) 
 // fp32 redo of a fixed-point step whose records overflowed the scale (grid
 // scatter of the levels that went in as fixed point only, no dW; the launch
 // exits at once unless *F.redo is set).
-template <int CACHE, bool ABL, int GM>
+// DET = 1 (deterministic mode, with GM 1; an int like GM, the only bool of
+// the list stays ABL): chunk c of the plan goes to block
+// c mod gridDim.x, each block takes its chunks in ascending order (no ticket
+// queue), and the block's dW goes with plain stores to its own slot
+// a.dw[blockIdx.x][K][FIELD_PARAMS] (zeroed by the entry) instead of atomics
+// into the shared gradient: a block's partial depends on the plan alone, and
+// rn_reduce_partials sums the slots in block order.
+template <int CACHE, bool ABL, int GM, int DET = 0>
 __global__ void __launch_bounds__(BWD_WAVES * 64)
 k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
     if (GM == 3 && __builtin_nontemporal_load(F.redo) == 0) return;   // uniform: whole grid exits
@@ -1231,7 +1243,10 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
     const __amdgpu_buffer_rsrc_t rows_rs = rn_rsrc(rows, (uint32_t)m.rows_cap * MB_ROW * 4u);
     int n_local = 0;
     int ticket = 0, n_chunks = 0;
-    if (threadIdx.x == 0) { n_chunks = m.queue[1]; ticket = atomicAdd(m.queue, 1); }
+    if (threadIdx.x == 0) {
+        n_chunks = m.queue[1];
+        ticket = DET ? (int)blockIdx.x : atomicAdd(m.queue, 1);
+    }
     if (threadIdx.x < K) sCh[2 + 3 * MB_KMAX + threadIdx.x] = a.seg_base[threadIdx.x];
 
     for (;;) {
@@ -1240,7 +1255,8 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
             // this chunk's descriptor (one 80-B load; its ticket was taken
             // during the previous chunk) and the next chunk's ticket
             const int ch = ticket;
-            ticket = atomicAdd(m.queue, 1);
+            // (DET: past the last chunk the ticket stops, so it cannot wrap)
+            ticket = DET ? (ch < n_chunks ? ch + (int)gridDim.x : ch) : atomicAdd(m.queue, 1);
             int4 d[CH_DESC / 4];
             if (ch < n_chunks) {
 #pragma unroll
@@ -1533,8 +1549,13 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
             f32x16 A, Bm;
             if (k == cur_k) { sc = cur; A = accA; Bm = accB; }
             else if (sc.a != 0.f || sc.b != 0.f) dw_unpark(park + (size_t)k * BWD_WAVES * 2048, A, Bm);
-            if (sc.a != 0.f || sc.b != 0.f)
-                dw_flush_owned(A, Bm, a.dw + (size_t)k * FIELD_PARAMS, wid, sc);
+            if (sc.a != 0.f || sc.b != 0.f) {
+                if (DET)
+                    dw_flush_owned<true>(A, Bm, a.dw + ((size_t)blockIdx.x * K + k) * FIELD_PARAMS,
+                                         wid, sc);
+                else
+                    dw_flush_owned(A, Bm, a.dw + (size_t)k * FIELD_PARAMS, wid, sc);
+            }
         }
     }
 }
@@ -2773,6 +2794,64 @@ int rn_field_bwd_merged(const float* ts, const int32_t* ray_of, const float* ray
         if (feat_cache) k_field_bwd_merged<CACHE_READ, false, 0><<<blocks, blk, 0, st>>>(a, m, G, F);
         else k_field_bwd_merged<CACHE_NONE, false, 0><<<blocks, blk, 0, st>>>(a, m, G, F);
     }
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+// Deterministic merged backward: the integer-grid kernel on the static chunk
+// schedule, dW into per-block slots (k_field_bwd_merged DET).
+int rn_field_bwd_merged_det(const float* ts, const int32_t* ray_of, const float* rays_o,
+                            const float* rays_d, const int32_t* seg_base,
+                            const int32_t* seg_count, const int32_t* mstart, const int32_t* perm,
+                            const int32_t* chunk_desc, const int32_t* queue, int64_t n_rays,
+                            int32_t n_models, int32_t max_samples, const void* grid_f16,
+                            const uint32_t* level_offset, const uint32_t* level_hsize,
+                            const uint32_t* level_res, const float* level_scale,
+                            const float* xyz_min, const float* extent, const void* frags,
+                            const float* dL_dsigma, const float* dL_drgb, float* grid_grad,
+                            float* dw_part, const void* feat_cache, float* scratch,
+                            int64_t scratch_rows, float* park, int32_t max_chunk, int32_t blocks,
+                            int32_t* igrad_lo, int32_t* igrad_carry, const float* igrad_scale,
+                            void* stream) {
+    RN_CHECK_ARG(igrad_lo && igrad_carry && igrad_scale,
+                 "the deterministic backward needs igrad_lo, igrad_carry and igrad_scale");
+    RN_CHECK_ARG(dw_part, "the deterministic backward needs dw_part");
+    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1 && n_models <= MB_KMAX && blocks >= 1 &&
+                 max_samples >= 1 && max_chunk >= 1, "bad sizes");
+    RN_CHECK_ARG(scratch_rows >= (int64_t)max_chunk + (int64_t)n_models * max_samples,
+                 "scratch_rows must be >= max_chunk + n_models * max_samples");
+    RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count && mstart &&
+                 perm && chunk_desc && queue && grid_f16 && level_offset && level_hsize && level_res &&
+                 level_scale && xyz_min && extent && frags && dL_dsigma && dL_drgb && grid_grad &&
+                 scratch && park, "null pointer");
+    FieldArgs a{};
+    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
+    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    a.dsigma = dL_dsigma; a.drgb = dL_drgb; a.grid_grad = grid_grad;
+    a.dw = dw_part;                              // [blocks][K][FIELD_PARAMS]
+    a.feat = (rn_half*)feat_cache;
+    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
+    a.seg_base = seg_base; a.seg_count = seg_count;
+    MergeArgs m{};
+    m.mstart = mstart; m.perm = perm; m.desc = chunk_desc;
+    m.queue = const_cast<int32_t*>(queue);       // only [1], the chunk count, is read
+    m.scratch = scratch; m.park = park;
+    m.n_rays = (int)n_rays; m.n_models = n_models; m.rows_cap = (int)scratch_rows;
+    hipStream_t st = (hipStream_t)stream;
+    // a block writes only the tiles of the models it met: everything else of
+    // its slot reads as zero
+    if (hipMemsetAsync(dw_part, 0, (size_t)blocks * n_models * FIELD_PARAMS * sizeof(float), st) !=
+        hipSuccess) {
+        rn_set_error("%s: dw_part reset failed", __func__);
+        return 2;
+    }
+    IntGrad G{};
+    G.bytes = 2 * a.grid_bytes;
+    G.lo_ptr = igrad_lo; G.carry_ptr = igrad_carry; G.scale_ptr = igrad_scale;
+    FxGrad F{};
+    const dim3 blk(BWD_WAVES * 64);
+    if (feat_cache) k_field_bwd_merged<CACHE_READ, false, 1, 1><<<blocks, blk, 0, st>>>(a, m, G, F);
+    else k_field_bwd_merged<CACHE_NONE, false, 1, 1><<<blocks, blk, 0, st>>>(a, m, G, F);
     RN_CHECK_LAUNCH();
     return 0;
 }

@@ -185,8 +185,15 @@ __device__ __forceinline__ void rn_dw_tile_gate_in(const rn_half* img_y, int ya,
     }
 }
 
-__global__ void __launch_bounds__(GATE_WAVES * 64)
+// DET (deterministic mode): one wave per block, so the adds into sDW run in
+// the wave's program order (each lane of a tile's atomic hits its own
+// address), tiles strided by gridDim.x, and the block's dW stored whole into
+// its own slot a.dw[blockIdx.x][n_params] (rn_reduce_partials sums the slots
+// in block order) instead of added into the shared gradient.
+template <bool DET>
+__global__ void __launch_bounds__(DET ? 64 : GATE_WAVES * 64)
 k_gate_bwd(GateArgs a) {
+    constexpr int NW = DET ? 1 : GATE_WAVES;
     __shared__ __attribute__((aligned(16))) rn_half sW[GATE_FRAGS * RN_FRAG_HALFS];
     __shared__ __attribute__((aligned(16))) rn_half sImg[GATE_WAVES * 2 * RN_IMG_HALFS];
     __shared__ __attribute__((aligned(16))) float sDW[GATE_MAX_PARAMS];
@@ -199,8 +206,8 @@ k_gate_bwd(GateArgs a) {
     rn_half* imgX = imgY + RN_IMG_HALFS;
     const half8 z8 = rn_zero8();
     const int64_t n_tiles = (a.n_rays + 31) / 32;
-    for (int64_t tile = (int64_t)blockIdx.x * GATE_WAVES + wid; tile < n_tiles;
-         tile += (int64_t)gridDim.x * GATE_WAVES) {
+    for (int64_t tile = (int64_t)blockIdx.x * NW + wid; tile < n_tiles;
+         tile += (int64_t)gridDim.x * NW) {
         rn_lds_order();   // weights stay in LDS: no hoisting of fragment reads
         const int64_t r = tile * 32 + c;
         const bool valid = r < a.n_rays;
@@ -298,6 +305,11 @@ k_gate_bwd(GateArgs a) {
         rn_lds_order();
     }
     __syncthreads();
+    if (DET) {
+        float* slot = a.dw + (size_t)blockIdx.x * a.n_params;
+        for (int i = threadIdx.x; i < a.n_params; i += blockDim.x) slot[i] = sDW[i];
+        return;
+    }
     for (int i = threadIdx.x; i < a.n_params; i += blockDim.x) {
         const float v = sDW[i];
         if (v != 0.f) atomicAdd(&a.dw[i], v);
@@ -336,7 +348,36 @@ int rn_gate_bwd(const float* in0, const float* in1, int32_t stride, int64_t n_ra
     a.n_params = n_params;
     RN_CHECK_ARG(!dL_dinput || dinput_frags, "the input gradient needs dinput_frags");
     a.dfrags = (const rn_half*)dinput_frags; a.dx = dL_dinput;
-    k_gate_bwd<<<n_blocks, GATE_WAVES * 64, 0, (hipStream_t)stream>>>(a);
+    k_gate_bwd<false><<<n_blocks, GATE_WAVES * 64, 0, (hipStream_t)stream>>>(a);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_gate_bwd_det(const float* in0, const float* in1, int32_t stride, int64_t n_rays,
+                    int32_t n_models, const void* frags, const float* dL_dgate, float* gate_part,
+                    int32_t n_params, const void* dinput_frags, float* dL_dinput,
+                    int32_t n_blocks, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_models >= 1 && n_models <= 16 && n_blocks >= 1, "bad sizes");
+    RN_CHECK_ARG(n_params == 12672 + 64 * n_models, "n_params mismatch");
+    RN_CHECK_ARG(gate_part, "null gate_part");
+    if (n_rays == 0) {
+        // no ray: every slot is zero
+        if (hipMemsetAsync(gate_part, 0, (size_t)n_blocks * n_params * sizeof(float),
+                           (hipStream_t)stream) != hipSuccess) {
+            rn_set_error("rn_gate_bwd_det: hipMemsetAsync failed");
+            return 2;
+        }
+        return 0;
+    }
+    RN_CHECK_ARG(in0 && in1 && frags && dL_dgate && stride >= 3, "null pointer / bad stride");
+    GateArgs a{};
+    a.in0 = in0; a.in1 = in1; a.stride = stride; a.n_rays = n_rays; a.K = n_models;
+    a.frags = (const rn_half*)frags; a.dgate = dL_dgate; a.dw = gate_part;
+    a.n_params = n_params;
+    RN_CHECK_ARG(!dL_dinput || dinput_frags, "the input gradient needs dinput_frags");
+    a.dfrags = (const rn_half*)dinput_frags; a.dx = dL_dinput;
+    // one wave per block: every block writes its whole slot (zeros included)
+    k_gate_bwd<true><<<n_blocks, 64, 0, (hipStream_t)stream>>>(a);
     RN_CHECK_LAUNCH();
     return 0;
 }

@@ -19,6 +19,11 @@ namespace {
 // loss_out: [0] sum over (B,3) of (rgb - t)^2, [1] sum over B of -o log o
 // (lambda applied), [2] cv^2 term (lambda applied), [3] sum over (B,K) of the
 // depth-mutual term (lambda applied).  The host divides by the element counts.
+// DET (deterministic mode): loss_out is the per-block partial buffer
+// [gridDim.x][4] instead -- block b stores its three sums into row b (no
+// atomics; block 0 keeps the cv^2 term in [0][2]) and k_loss_sum adds the rows
+// in block order.  The per-ray part and the seeds are the same code.
+template <bool DET>
 __global__ void __launch_bounds__(256)
 k_nerf_loss(int64_t B, int K, const float* __restrict__ rgb, const float* __restrict__ target,
             const float* __restrict__ opacity, const float* __restrict__ depth,
@@ -92,9 +97,61 @@ k_nerf_loss(int64_t B, int K, const float* __restrict__ rgb, const float* __rest
     if (threadIdx.x < 3) {
         float x = 0.f;
         for (int w = 0; w < (int)(blockDim.x / RN_WAVE); ++w) x += red[threadIdx.x][w];
-        atomicAdd(&loss_out[threadIdx.x == 2 ? 3 : threadIdx.x], x);
+        const int q = threadIdx.x == 2 ? 3 : threadIdx.x;
+        if (DET) loss_out[4 * (size_t)blockIdx.x + q] = x;
+        else atomicAdd(&loss_out[q], x);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && use_cv) loss_out[2] = lambda_cv * var / den;
+}
+
+// deterministic mode: the blocks' partial sums of k_nerf_loss<true> in block
+// order, one thread per term; the cv^2 term is block 0's
+__global__ void k_loss_sum(const float* __restrict__ part, int n_blocks, int use_cv,
+                           float* __restrict__ loss_out) {
+    const int q = threadIdx.x;
+    if (q >= 4) return;
+    if (q == 2) { loss_out[2] = use_cv ? part[2] : 0.f; return; }
+    float acc = 0.f;
+    for (int b = 0; b < n_blocks; ++b) acc += part[4 * (size_t)b + q];
+    loss_out[q] = acc;
+}
+
+// out[i] = (...((out[i] + part[0][i]) + part[1][i]) + ...) + part[n_slots - 1][i]:
+// one thread per i, plain fp32 adds in ascending slot order (the order is the
+// contract: include/radnerf.h), loads coalesced over i
+__global__ void __launch_bounds__(256)
+k_reduce_partials(const float* __restrict__ part, int n_slots, int64_t n,
+                  float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float acc = out[i];
+    const float* p = part + i;
+#pragma unroll 8
+    for (int s = 0; s < n_slots; ++s) acc += p[(size_t)s * n];
+    out[i] = acc;
+}
+
+// out[c] = sum over rows of x[r][c], block c = column c, one wave: lane l adds
+// the sums of the 32-row tiles l, l + 64, ... in ascending order (each tile
+// summed row by row from 0), then a fixed xor butterfly over the lanes.  The
+// tree depends on (rows, cols) alone; no atomics.
+constexpr int RN_COLSUM_TILE = 32;
+
+__global__ void __launch_bounds__(RN_WAVE)
+k_colsum_ordered(const float* __restrict__ x, int64_t rows, int cols, float* __restrict__ out) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int64_t n_tiles = (rows + RN_COLSUM_TILE - 1) / RN_COLSUM_TILE;
+    float acc = 0.f;
+    for (int64_t t = lane; t < n_tiles; t += RN_WAVE) {
+        const int64_t r0 = t * RN_COLSUM_TILE;
+        const int64_t r1 = r0 + RN_COLSUM_TILE < rows ? r0 + RN_COLSUM_TILE : rows;
+        float s = 0.f;
+        for (int64_t r = r0; r < r1; ++r) s += x[r * cols + c];
+        acc += s;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) out[c] = acc;
 }
 
 // Adam with bias correction, in torch.optim.Adam's operation order (no weight
@@ -259,9 +316,48 @@ int rn_nerf_loss(const float* rgb, const float* target_rgb, const float* opacity
         rn_set_error("rn_nerf_loss: hipMemsetAsync failed");
         return 2;
     }
-    k_nerf_loss<<<nblk(n_rays, 256), 256, 0, (hipStream_t)stream>>>(
+    k_nerf_loss<false><<<nblk(n_rays, 256), 256, 0, (hipStream_t)stream>>>(
         n_rays, n_models, rgb, target_rgb, opacity, depth, gate, importance, lambda_opacity,
         lambda_cv, lambda_dm, loss_out, dL_drgb, dL_dopacity, dL_ddepth, dL_dgate);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_nerf_loss_det(const float* rgb, const float* target_rgb, const float* opacity,
+                     const float* depth, const float* gate, const float* importance,
+                     int64_t n_rays, int32_t n_models, float lambda_opacity, float lambda_cv,
+                     float lambda_dm, float* loss_out, float* part, float* dL_drgb,
+                     float* dL_dopacity, float* dL_ddepth, float* dL_dgate, void* stream) {
+    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1, "bad sizes");
+    RN_CHECK_ARG(rgb && target_rgb && opacity && depth && gate && importance && loss_out && part &&
+                 dL_drgb && dL_dopacity && dL_ddepth && dL_dgate, "null pointer");
+    RN_CHECK_ARG(nblk(n_rays, 256) <= 0x7fffffff / 4, "too many rays");
+    const int nb = nblk(n_rays, 256);
+    // the same test as the kernel's use_cv
+    const int use_cv = n_models > 1 && lambda_cv > 0.f;
+    k_nerf_loss<true><<<nb, 256, 0, (hipStream_t)stream>>>(
+        n_rays, n_models, rgb, target_rgb, opacity, depth, gate, importance, lambda_opacity,
+        lambda_cv, lambda_dm, part, dL_drgb, dL_dopacity, dL_ddepth, dL_dgate);
+    RN_CHECK_LAUNCH();
+    k_loss_sum<<<1, 64, 0, (hipStream_t)stream>>>(part, nb, use_cv, loss_out);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_reduce_partials(const float* part, int32_t n_slots, int64_t n, float* out, void* stream) {
+    RN_CHECK_ARG(n_slots >= 1 && n >= 0, "bad sizes");
+    RN_CHECK_ARG(part && out, "null pointer");
+    if (n == 0) return 0;
+    RN_CHECK_ARG((n + 255) / 256 <= 0x7fffffff, "n too large");
+    k_reduce_partials<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(part, n_slots, n, out);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_colsum_ordered(const float* x, int64_t rows, int32_t cols, float* out, void* stream) {
+    RN_CHECK_ARG(rows >= 0 && cols >= 1 && cols <= 16, "rows >= 0, cols in 1..16");
+    RN_CHECK_ARG(out && (rows == 0 || x), "null pointer");
+    k_colsum_ordered<<<cols, RN_WAVE, 0, (hipStream_t)stream>>>(x, rows, cols, out);
     RN_CHECK_LAUNCH();
     return 0;
 }

@@ -91,6 +91,13 @@ SIGNATURES = {
     "rn_gate_bwd": [P, P, I32, I64, I32, P, P, P, I32, P, P, I32, P],
     "rn_nerf_loss": [P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P, P, P, P],
     "rn_adam": [P, P, P, P, I64, F64, F64, F64, F64, I32, F32, P, I64, P],
+    # deterministic training (FusedMLRenderer(deterministic=True))
+    "rn_reduce_partials": [P, I32, I64, P, P],
+    "rn_colsum_ordered": [P, I64, I32, P, P],
+    "rn_field_bwd_merged_det": [P, P, P, P, P, P, P, P, P, P, I64, I32, I32, P, P, P, P, P, P,
+                                P, P, P, P, P, P, P, P, I64, P, I32, I32, P, P, P, P],
+    "rn_gate_bwd_det": [P, P, I32, I64, I32, P, P, P, I32, P, P, I32, P],
+    "rn_nerf_loss_det": [P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P, P, P, P, P],
     "rn_get_rays": [P, P, P, P, I64, P, P, P, P, P],
     "rn_get_rays_pose": [P, P, P, P, P, P, I64, P, P, P, P, P],
     "rn_get_rays_pose_bw": [P, P, P, P, P, I64, I64, P, P, P, P, P, P, P],

@@ -190,7 +190,23 @@ class FusedMLRenderer:
     """Owns the workspace and runs the fused forward / backward chains."""
 
     def __init__(self, model, gating_net, n_rays, device=None, fwd_blocks=None, bwd_blocks=None,
-                 capacity=None):
+                 capacity=None, deterministic=False):
+        """deterministic=True: bitwise-reproducible steps (DESIGN.md §4
+        "Deterministic training").  On one GPU in one process the same
+        parameters, inputs and seed then give the same gradients, loss terms
+        and outputs whatever the order blocks and waves run in: the merged
+        backward takes its chunks on a static schedule and writes per-block dW
+        slots (rn_field_bwd_merged_det, the integer-grid form), the gate
+        backward per-block slots too (rn_gate_bwd_det), both summed in slot
+        order (rn_reduce_partials); the gate importance and the loss terms are
+        ordered sums (rn_colsum_ordered, rn_nerf_loss_det).  ValueError above 8
+        sub-NeRFs or with merged_bwd off (the per-model backward scatters with
+        fp32 atomics).  Under data parallelism each rank's local gradient is
+        reproducible; the order of the collective's sum is RCCL's."""
+        self._deterministic = self._merged_bwd = False
+        if deterministic and not 1 <= model.size <= 8:
+            # refused before the workspace is allocated
+            raise ValueError(self._NO_DET + f" (this model: {model.size} sub-NeRFs)")
         self.model, self.gate = model, gating_net
         self.device = device or model.mlp_params.device
         self.ws = Workspace(n_rays, model.size, self.device, capacity=capacity)
@@ -268,8 +284,13 @@ class FusedMLRenderer:
         # returning u32 atomics with carries + rn_igrad_to_f32): bitwise
         # reproducible grid gradients, but each issue waits for the previous
         # one's return (the compiler's vmcnt(0)): 4.33 vs 3.81 ms on C3, so the
-        # default stays fp32 atomics
+        # default stays fp32 atomics (against today's fixed-point / binned
+        # defaults, train steps: C3 4.73 vs 4.21 ms, C5 per GPU 11.65 vs 7.90;
+        # tools/deterministic_step.py, profiles/deterministic/)
         self.int_grad = False
+        # bitwise-reproducible steps (see __init__); the grid gradient then
+        # takes the int_grad form whatever the switches below say
+        self.deterministic = bool(deterministic)
         # fixed-point accumulation of the hashed levels' grid gradient (u32
         # adds, scale from the previous step's largest record, fp32 redo on
         # overflow; rn_grid_fx_fold): field_bwd C3 3.76 -> 3.50 ms, C4 per
@@ -375,6 +396,31 @@ class FusedMLRenderer:
         self.trace = False
         self.events = {}
 
+    _NO_DET = ("FusedMLRenderer(deterministic=True) needs the merged backward (1 to 8 sub-NeRFs, "
+               "merged_bwd on): the per-model backward scatters the grid gradient and dW with "
+               "fp32 atomics in arrival order")
+
+    @property
+    def merged_bwd(self):
+        return self._merged_bwd
+
+    @merged_bwd.setter
+    def merged_bwd(self, on):
+        if self._deterministic and not on:
+            raise ValueError(self._NO_DET)
+        self._merged_bwd = bool(on)
+
+    @property
+    def deterministic(self):
+        return self._deterministic
+
+    @deterministic.setter
+    def deterministic(self, on):
+        if on and not self._merged_bwd:
+            raise ValueError(self._NO_DET + f" (this renderer: {self.model.size} sub-NeRFs, "
+                             f"merged_bwd {self._merged_bwd})")
+        self._deterministic = bool(on)
+
     @property
     def scatter_mode(self):
         """How the next backward accumulates the grid gradient, from the
@@ -386,7 +432,7 @@ class FusedMLRenderer:
         fp32 atomics, whatever they say."""
         if not self.merged_bwd:
             return "fp32-atomics"
-        if self.int_grad:
+        if self.int_grad or self.deterministic:
             return "int-grad"
         if self.grid_fx and self.feat_cache:
             return "binned" if self.grid_bin else "fixed-point"
@@ -469,8 +515,13 @@ class FusedMLRenderer:
             frags = g.packed_frags()          # (re)packed on the main stream
             side.wait_stream(main)
             self._ev("gate_fwd", L.gate_fwd, rays_o.data_ptr(), gate_in2.data_ptr(), 3, B, G,
-                     frags.data_ptr(), out_gate.data_ptr(), imp.data_ptr(),
+                     frags.data_ptr(), out_gate.data_ptr(),
+                     None if self.deterministic else imp.data_ptr(),
                      max(1, min(256, (B + 127) // 128)), side.cuda_stream, stream=side)
+            if self.deterministic:
+                # gate.sum(0) as an ordered sum instead of one atomic per wave
+                self._ev("gate_colsum", L.colsum_ordered, out_gate.data_ptr(), B, G,
+                         imp.data_ptr(), side.cuda_stream, stream=side)
         bits = self.bitfields()
         march = (rays_o.data_ptr(), rays_d.data_ptr(), m.center.data_ptr(),
                  m.half_size.data_ptr(), NEAR_DISTANCE, noise.data_ptr(), bits.data_ptr(),
@@ -590,6 +641,9 @@ class FusedMLRenderer:
                     self.merged_blocks if self.balance_chunks else 0):
                 self._plan(st)      # chunk sizes changed since the forward
             chunks = self._chunks
+            if self.deterministic:
+                self._field_bwd_det(rays_o, rays_d, st, grid_grad, dw, common, rows, scratch, park)
+                return
             ig = (None, None, None)
             fx = (None, None, None, None, 0)
             gb = (None, None, None, 0)
@@ -614,13 +668,7 @@ class FusedMLRenderer:
                 gb = (pool["ctl"].data_ptr(), pool["meta"].data_ptr(), pool["recs"].data_ptr(),
                       pool["pages"])
             if self.int_grad:
-                n_g = grid_grad.numel()
-                if getattr(w, "_igrad", None) is None or w._igrad[0].numel() != n_g:
-                    z = dict(device=grid_grad.device, dtype=torch.int32)
-                    w._igrad = (torch.zeros(n_g, **z), torch.zeros(n_g, **z),
-                                torch.ones(1, device=grid_grad.device),
-                                torch.zeros(1, **z))
-                lo, carry, scale, work = w._igrad
+                lo, carry, scale, work = self._igrad_buffers(grid_grad)
                 self._ev("seed_scale", L.seed_scale, w.seg_base.data_ptr(),
                          w.seg_count.data_ptr(), m.size, w.sigma.data_ptr(), w.dsigma.data_ptr(),
                          w.drgb.data_ptr(), work.data_ptr(), scale.data_ptr(), st)
@@ -716,6 +764,46 @@ class FusedMLRenderer:
             if self.after_grid_levels is not None:
                 self.after_grid_levels(0)
 
+    def _igrad_buffers(self, grid_grad):
+        """Integer-grid state (rn_seed_scale, rn_igrad_to_f32): lo / carry words
+        per gradient element (zero between steps), the step's scale and the
+        scale's scratch word."""
+        w, n_g = self.ws, grid_grad.numel()
+        if getattr(w, "_igrad", None) is None or w._igrad[0].numel() != n_g:
+            z = dict(device=grid_grad.device, dtype=torch.int32)
+            w._igrad = (torch.zeros(n_g, **z), torch.zeros(n_g, **z),
+                        torch.ones(1, device=grid_grad.device), torch.zeros(1, **z))
+        return w._igrad
+
+    def _field_bwd_det(self, rays_o, rays_d, st, grid_grad, dw, common, rows, scratch, park):
+        """The deterministic merged backward: integer grid sums (order-free),
+        chunk c on block c mod merged_blocks, each block's dW in its own slot
+        of ws.dw_part, the slots added into dw in block order."""
+        m, w, L = self.model, self.ws, lib()
+        lo, carry, scale, work = self._igrad_buffers(grid_grad)
+        n_dw = m.size * LY.FIELD_PARAMS
+        if getattr(w, "dw_part", None) is None or w.dw_part.shape != (self.merged_blocks, n_dw):
+            w.dw_part = torch.empty(self.merged_blocks, n_dw, device=grid_grad.device)
+        self._ev("seed_scale", L.seed_scale, w.seg_base.data_ptr(), w.seg_count.data_ptr(),
+                 m.size, w.sigma.data_ptr(), w.dsigma.data_ptr(), w.drgb.data_ptr(),
+                 work.data_ptr(), scale.data_ptr(), st)
+        self._ev("field_bwd", L.field_bwd_merged_det, w.ts.data_ptr(), w.ray_of.data_ptr(),
+                 rays_o.data_ptr(), rays_d.data_ptr(), w.seg_base.data_ptr(),
+                 w.seg_count.data_ptr(), w.mstart.data_ptr(), w.perm.data_ptr(),
+                 w._chunk_desc.data_ptr(), w.queue.data_ptr(), w.B, m.size, MAX_SAMPLES,
+                 *common[10:], w.dsigma.data_ptr(), w.drgb.data_ptr(), grid_grad.data_ptr(),
+                 w.dw_part.data_ptr(), w.feat.data_ptr() if self.feat_cache else None,
+                 scratch.data_ptr(), rows, park.data_ptr(), self.max_chunk, self.merged_blocks,
+                 lo.data_ptr(), carry.data_ptr(), scale.data_ptr(), st)
+        self._ev("dw_reduce", L.reduce_partials, w.dw_part.data_ptr(), self.merged_blocks, n_dw,
+                 dw.data_ptr(), st)
+        if self.after_field_bwd is not None:
+            self.after_field_bwd()          # the MLP gradient is final here
+        self._ev("igrad_to_f32", L.igrad_to_f32, grid_grad.numel(), lo.data_ptr(),
+                 carry.data_ptr(), scale.data_ptr(), grid_grad.data_ptr(), st)
+        if self.after_grid_levels is not None:
+            self.after_grid_levels(0)
+
     # pool growth reads the page count of the binned backward this many
     # backwards back, waiting for it if needed (ADVICE r04: reading whichever
     # count had arrived made the pool size -- and so which steps after an
@@ -805,11 +893,26 @@ class FusedMLRenderer:
             frags = g.packed_frags()
             if stream is side:
                 side.wait_stream(main)
+            n_blk = max(1, min(128, (B + 127) // 128))
+            if self.deterministic:
+                # one wave per block into the block's slot of ws.gate_part, the
+                # slots added into gate_grad in block order, on the gate's stream
+                n_par = gate_grad.numel()
+                if getattr(w, "gate_part", None) is None or w.gate_part.shape != (n_blk, n_par):
+                    w.gate_part = torch.empty(n_blk, n_par, device=dev)
+                self._ev("gate_bwd", L.gate_bwd_det, rays_o.data_ptr(), gate_in2.data_ptr(), 3,
+                         B, G, frags.data_ptr(), dgate.data_ptr(), w.gate_part.data_ptr(), n_par,
+                         None if gate_dfr is None else gate_dfr.data_ptr(),
+                         None if gate_dx is None else gate_dx.data_ptr(), n_blk,
+                         stream.cuda_stream, stream=stream)
+                self._ev("gate_reduce", L.reduce_partials, w.gate_part.data_ptr(), n_blk, n_par,
+                         gate_grad.data_ptr(), stream.cuda_stream, stream=stream)
+                return
             self._ev("gate_bwd", L.gate_bwd, rays_o.data_ptr(), gate_in2.data_ptr(), 3, B, G,
                      frags.data_ptr(), dgate.data_ptr(), gate_grad.data_ptr(),
                      gate_grad.numel(), None if gate_dfr is None else gate_dfr.data_ptr(),
                      None if gate_dx is None else gate_dx.data_ptr(),
-                     max(1, min(128, (B + 127) // 128)), stream.cuda_stream, stream=stream)
+                     n_blk, stream.cuda_stream, stream=stream)
 
         # gate backward: it only needs dL/dgate (combine_bw)
         gate_at = self.gate_bwd_at if self.gate_grad_here else None
@@ -912,9 +1015,14 @@ class FusedMLRenderer:
         dist = lambda_distortion > 0
         rgb, opacity, depth, gate, imp = self.forward(rays_o, rays_d, gate_in2, noise, bg,
                                                       T_threshold, exp_step_factor, dist)
+        # the step's render, for callers that log it (train_step returns the
+        # loss terms and the gradients only)
+        self.last_forward = {"rgb": rgb, "opacity": opacity, "depth": depth, "gate": gate,
+                             "importance": imp}
         terms, (d_rgb, d_op, d_depth, d_gate) = fused_nerf_loss(
             rgb, target_rgb, opacity, depth, gate, imp, lambda_opacity, lambda_cv_importance,
-            lambda_depth_mutual, lambda_distortion, self.ws.dist_k if dist else None)
+            lambda_depth_mutual, lambda_distortion, self.ws.dist_k if dist else None,
+            deterministic=self.deterministic)
         d_dist = float(lambda_distortion) / rays_o.shape[0] if dist else None
         if not input_grad:
             grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
@@ -1023,16 +1131,19 @@ _RENDERERS = collections.OrderedDict()
 MAX_RENDERERS = 4
 
 
-def get_renderer(model, gating_net, n_rays, grad=True):
+def get_renderer(model, gating_net, n_rays, grad=True, deterministic=False):
     """The cached renderer (and workspace) of (model, gate, batch size).
     Renders without autograd (grad=False) get their own workspace, so a
     logging / validation render between a forward and its backward does not
     overwrite the samples the backward reads.  Least recently used entries
-    beyond MAX_RENDERERS are dropped (their workspaces freed)."""
+    beyond MAX_RENDERERS are dropped (their workspaces freed).  deterministic:
+    FusedMLRenderer(deterministic=True), a renderer of its own."""
     key = (id(model), id(gating_net), n_rays, str(model.mlp_params.device), bool(grad))
+    if deterministic:
+        key += (True,)
     r = _RENDERERS.get(key)
     if r is None or r.model is not model or r.gate is not gating_net:
-        r = FusedMLRenderer(model, gating_net, n_rays)
+        r = FusedMLRenderer(model, gating_net, n_rays, deterministic=bool(deterministic))
         _RENDERERS[key] = r
     _RENDERERS.move_to_end(key)
     while len(_RENDERERS) > MAX_RENDERERS:
@@ -1053,7 +1164,9 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     Mip-NeRF 360 distortion loss of sub-NeRF i (DistortionLoss.apply on its
     ws / deltas / ts / rays_a; not gate-weighted, losses.py:63-67), computed
     and differentiated inside the composite kernels.  NeRFLoss(lambda_distortion
-    > 0) reads it."""
+    > 0) reads it.  deterministic=True renders through a
+    FusedMLRenderer(deterministic=True), a renderer and workspace of its own:
+    the backward's gradients are then bitwise reproducible."""
     rays_o, rays_d = rays_o.float().contiguous(), rays_d.float().contiguous()
     second = imgs_d.float().contiguous() if gating_net.type == "image" else rays_d
     B, K, dev = rays_o.shape[0], model.size, rays_o.device
@@ -1067,7 +1180,8 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
         bg = torch.rand(3, device=dev)
     else:
         bg = torch.zeros(3, device=dev)
-    r = get_renderer(model, gating_net, B, grad=torch.is_grad_enabled())
+    r = get_renderer(model, gating_net, B, grad=torch.is_grad_enabled(),
+                     deterministic=bool(kwargs.get("deterministic", False)))
     distortion = bool(kwargs.get("distortion", False))
     fn_args = (model.xyz_encoder.params, model.mlp_params, gating_net.params, r, rays_o, rays_d,
                second, noise.contiguous(), bg, float(kwargs.get("T_threshold", 1e-4)), esf)

@@ -72,6 +72,11 @@ class PinnedMLRenderer(FusedMLRenderer):
         in this one process (bench.py --pinned-sim: its sub-NeRFs over all B
         rays, the gate backward if rank 0), the all-gather replaced by local
         copies of this rank's rows (the other ranks' rows are stand-ins)."""
+        if kw.get("deterministic", False):
+            raise ValueError(
+                "PinnedMLRenderer(deterministic=True): the sub-NeRF-per-GPU layout sums the "
+                "shared grid's gradient across ranks in the collective's order, which the "
+                "deterministic mode does not cover; use FusedMLRenderer on one GPU")
         self.group = group
         self.simulated = sim is not None
         if self.simulated:

@@ -249,7 +249,8 @@ def _train_fused(model, rays_o, rays_d, kw):
     if noise is not None:
         kw["noise"] = noise.reshape(1, -1)
     res = ml_render_fused(model, gate, rays_o, rays_d, rays_d, **kw)
-    r = get_renderer(model, gate, rays_o.shape[0], grad=torch.is_grad_enabled())
+    r = get_renderer(model, gate, rays_o.shape[0], grad=torch.is_grad_enabled(),
+                     deterministic=bool(kw.get("deterministic", False)))
     base = {"rgb": res["rgb"], "opacity": res["opacity"], "depth": res["depth"][:, 0]}
     if "distortion" in res:
         base["distortion"] = res["distortion"][:, 0]

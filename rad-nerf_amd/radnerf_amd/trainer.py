@@ -42,7 +42,10 @@ rays (refined by dR / dT under optimize_ext) and fills the march jitter and
 the random background in one launch, all from a counter-based hash of
 (seed, global_step, rank): no torch generator, different pixels on every
 rank, and a trainer resumed with the same seed and global_step continues the
-same stream.  The consumed batch stays in `tr.last_batch`.  step and
+same stream of batches.  (The batches repeat; the step's gradients repeat bit
+for bit only with Trainer(deterministic=True), which replaces the step's fp32
+sums in arrival order by ordered ones -- DESIGN.md §4 "Deterministic
+training".)  The consumed batch stays in `tr.last_batch`.  step and
 step_pixels keep drawing from torch's generator.  fit sets the cosine
 schedule (sampler.cosine_lr, eta_min = lr / 30) on the network's parameter
 group at each epoch's start (the pose group keeps its lr, as the reference
@@ -91,7 +94,16 @@ class Trainer:
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
                  optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None, intrinsics=None,
-                 cull_invisible=False, erode=False):
+                 cull_invisible=False, erode=False, deterministic=False):
+        """deterministic=True: the renderer is FusedMLRenderer(deterministic=
+        True) (ValueError above 8 sub-NeRFs).  With step_sampled / fit, whose
+        batches are a hash of (seed, global_step, rank), every parameter, Adam
+        moment, density grid, bitfield and loss term after any number of steps
+        is then a function of the initial state and the seed, bit for bit, on
+        one GPU in one process (step / step_pixels without `noise` still draw
+        from torch's generator: seed it).  Under data parallelism each rank's
+        local gradient is reproducible; the collective sums the ranks in
+        RCCL's order, which this mode does not fix."""
         if optimize_ext and (directions is None or poses is None):
             raise ValueError("Trainer(optimize_ext=True) needs directions (P, 3) and poses "
                              "(N, 3, 4): the pose corrections are per image of `poses`")
@@ -131,7 +143,9 @@ class Trainer:
         self._evaluator = None
         self.model, self.gate = model, gating_net
         self.device = model.mlp_params.device
-        self.renderer = FusedMLRenderer(model, gating_net, n_rays)
+        self.deterministic = bool(deterministic)
+        self.renderer = FusedMLRenderer(model, gating_net, n_rays,
+                                        deterministic=self.deterministic)
         # train_ml.py:101-102: exp step 1/256 beyond scale 0.5
         self.esf = (1 / 256 if model.scale > 0.5 else 0.0) if exp_step_factor is None \
             else float(exp_step_factor)
