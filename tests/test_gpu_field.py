@@ -7,6 +7,10 @@ residual differences are fp32 summation order, occasionally flipping one f16
 ulp of an activation.  Tolerances (written per assertion):
   forward sigma, rgb:   |diff| <= 5e-3 + 1e-2*|ref|, and 99th pct <= 1e-3-level
   backward grads:       relative L2 per grid level / MLP layer (tests/parity.py)
+
+These are aggregate bars.  tests/test_gpu_mlp.py compares the same kernels per
+activation and per weight with the fp64 reference tests/mlp_ref.py and derived
+bounds (one wrong weight slot, SH coefficient, ReLU mask or dW row).
 """
 import numpy as np
 import pytest
