@@ -301,7 +301,7 @@ struct Walk2 {
     // integer mode: the two newest issues, checked for carries one issue late
     int32_t oldA, loA, hiA, oldB, loB, hiB;
     uint32_t offA, offB;
-    // fixed-point mode (GM 2): the scales of the wave's two levels (even
+    // fixed-point mode (GM_FX): the scales of the wave's two levels (even
     // streams: level wid, odd: 15 - wid; 0 = fp32 atomics for that level) and
     // the largest |record| issued for each, as float bits (NaN/inf included)
     float fxA, fxB;
@@ -313,7 +313,7 @@ struct Walk2 {
     // (fx_weight): two entries that wrap in opposite directions cancel in
     // the plain sum but not in this one
     uint64_t swA, swB;
-    // binned mode (GM 4): each level's open page in the pool and its fill,
+    // binned mode (GM_BIN): each level's open page in the pool and its fill,
     // and the levels' first entries (wave-uniform)
     uint32_t pgA, pgB, nA, nB, loffA, loffB;
     bool started;          // the chunk's first step has been walked (wave-uniform)
@@ -330,6 +330,25 @@ __device__ __forceinline__ void walk2_begin(Walk2& W, uint32_t* ring) {
     W.started = false;
 }
 
+// How the merged backward accumulates the grid gradient: k_field_bwd_merged's
+// and the walk's GM template argument.  rn_field_bwd_merged's public fx_mode
+// takes the same values (0 and 2-5; GM_INT is selected by igrad_lo), and
+// fused.py names them alike.
+enum : int {
+    GM_F32 = 0,        // fp32 atomics
+    GM_INT = 1,        // exact integer with carries (IntGrad)
+    GM_FX = 2,         // fixed point for the levels with a scale (FxGrad)
+    GM_FX_REDO = 3,    // fp32 redo of a flagged fixed-point / binned step
+    GM_BIN = 4,        // binned: page records (rn_bin.h)
+    GM_BIN_F32 = 5,    // binned, the even streams' levels (0-7) by fp32 atomics
+};
+// has per-level scales (FxGrad::scale; a zero scale = fp32 atomics for the level)
+constexpr bool gm_has_scales(int gm) { return gm >= GM_FX; }
+// appends page records to the pool instead of issuing atomics
+constexpr bool gm_pages(int gm) { return gm == GM_BIN || gm == GM_BIN_F32; }
+// the even streams are fp32 at compile time (no page code for them)
+constexpr bool gm_even_f32(int gm) { return gm == GM_BIN_F32; }
+
 // Exact integer accumulation of the grid gradient (IG mode).  Each record
 // value v becomes q = rint(v * 2^scale_exp) (int64), added as a 32-bit low
 // word with a returning atomic; the high word plus any signed overflow of the
@@ -342,8 +361,8 @@ struct IntGrad {
     float scale;                        // 2^scale_exp (loaded from scale_ptr)
     int32_t* lo_ptr; int32_t* carry_ptr; const float* scale_ptr;
     uint32_t bytes;
-    __amdgpu_buffer_rsrc_t fx;          // fixed-point mode (GM 2): FxGrad::acc
-    // binned mode (GM 4, rn_bin.h): the page pool the walk appends to
+    __amdgpu_buffer_rsrc_t fx;          // fixed-point mode (GM_FX): FxGrad::acc
+    // binned mode (GM_BIN, rn_bin.h): the page pool the walk appends to
     GbCtl* ctl; uint32_t* page_meta; uint64_t* pages; uint32_t pool_pages;
 };
 
@@ -355,7 +374,7 @@ __device__ __forceinline__ void ig_check(int32_t old, int32_t lo, int32_t hi, ui
     if (c != 0) __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(c, G.carry, (int)off, 0, 0);
 }
 
-// Fixed-point accumulation of the hashed levels' grid gradient (GM 2, the
+// Fixed-point accumulation of the hashed levels' grid gradient (GM_FX, the
 // default of the merged backward).  A record v of level l is added as the
 // int32 rint(v * 2^e_l) with a NON-returning u32 atomic into `acc` (same
 // layout as grid_grad): the memory side serves u32 adds at 26.6 G requests/s
@@ -367,7 +386,7 @@ __device__ __forceinline__ void ig_check(int32_t old, int32_t lo, int32_t hi, ui
 // level takes ~77 records per C3 step, of mixed sign, and its largest sum
 // stays within 2^1.2 of the largest record).  The kernel records this step's
 // largest |record| per level; when it reaches 2^30 units (8x growth) or is not
-// finite, rn_grid_fx_fold discards the fixed-point sums and the GM 3 launch
+// finite, rn_grid_fx_fold discards the fixed-point sums and the GM_FX_REDO launch
 // redoes the grid scatter in fp32.
 // The first step of a workspace (scale 0) uses fp32 atomics and measures the
 // records; the dense levels (few requests, but entries that sum hundreds of
@@ -407,7 +426,7 @@ struct FxGrad {
     uint32_t* vmax;            // FxStats::vmax
     int64_t* qsum;             // FxStats::qsum
     uint64_t* wq;              // FxStats::wq
-    const int32_t* redo;       // GM 3: the launch runs only when *redo != 0
+    const int32_t* redo;       // GM_FX_REDO: the launch runs only when *redo != 0
     __amdgpu_buffer_rsrc_t rs; // over acc (built in the kernel)
 };
 
@@ -426,16 +445,16 @@ __device__ __forceinline__ void walk2_issue(Walk2& W, int s, uint32_t cnt,
     const int lane = rn_lane();
     const uint32_t h = __builtin_amdgcn_readlane(W.head, 4 * s);
     constexpr bool odd = ODD;
-    // binned (GM 4); GM 5: binned with the even streams' levels (0-7) by fp32
+    // binned (GM_BIN); GM_BIN_F32: binned with the even streams' levels (0-7) by fp32
     // atomics, known at compile time -- that instantiation carries no page or
     // record-encoding code (round 6: the renderer's default at scale 16 sends
     // levels [0, 8-9) by fp32 atomics, FusedMLRenderer.bin_f32_levels)
-    constexpr bool BIN = GM == 4 || GM == 5;
-    constexpr bool F32S = GM == 5 && !ODD;
+    constexpr bool BIN = gm_pages(GM);
+    constexpr bool F32S = gm_even_f32(GM) && !ODD;
     // the level's scale as float bits selected on the scalar unit (gfx9 has
     // no scalar float compare: a float test here became a VALU compare + vcc
     // branch per issue)
-    const uint32_t scb = GM >= 2 ? (uint32_t)__builtin_amdgcn_readfirstlane(
+    const uint32_t scb = gm_has_scales(GM) ? (uint32_t)__builtin_amdgcn_readfirstlane(
                                        (int)(odd ? __float_as_uint(W.fxB) : __float_as_uint(W.fxA)))
                                  : 0u;
     const bool fx_lvl = !F32S && (scb << 1) != 0u;   // 2^e_l > 0: fixed point; +-0: fp32 atomics
@@ -459,7 +478,7 @@ __device__ __forceinline__ void walk2_issue(Walk2& W, int s, uint32_t cnt,
             if (odd) { W.pgB = np; W.nB = 0u; } else { W.pgA = np; W.nA = 0u; }
         }
     }
-    if (GM == 1) {
+    if (GM == GM_INT) {
         // the issue two back has had a whole issue's time to return
         ig_check(W.oldA, W.loA, W.hiA, W.offA, G);
         W.oldA = W.oldB; W.loA = W.loB; W.hiA = W.hiB; W.offA = W.offB;
@@ -469,13 +488,13 @@ __device__ __forceinline__ void walk2_issue(Walk2& W, int s, uint32_t cnt,
         const uint32_t rec = w2_wrap(h + (lane >> 1));
         const uint32_t* base = W.ring + s * 3 * W2_RING;
         const uint32_t w0 = base[rec];
-        // byte offset of the lane's feature (GM 4: only the fp32 fallback
+        // byte offset of the lane's feature (GM_BIN: only the fp32 fallback
         // and the timing branches use it; the page record takes w0)
         const uint32_t off = (BIN ? 8u * ((odd ? W.loffB : W.loffA) + w0) : w0) + 4u * (lane & 1);
         const uint32_t v = base[(1 + (lane & 1)) * W2_RING + rec];
         if (rn_dbg(dbg) & 1) {
             asm volatile("" :: "v"(off), "v"(v));
-        } else if (GM == 3 && !fx_lvl) {
+        } else if (GM == GM_FX_REDO && !fx_lvl) {
             // redo: this level went in with fp32 atomics in the first pass
         } else if (rn_dbg(dbg) & 64) {      // ablation: non-returning i32 adds (timing only)
             (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(
@@ -504,7 +523,7 @@ __device__ __forceinline__ void walk2_issue(Walk2& W, int s, uint32_t cnt,
                 if (rn_dbg(dbg) & 8) *dst = word;                // (timing only: plain stores)
                 else __builtin_nontemporal_store(word, dst);
             }
-        } else if (GM == 2) {
+        } else if (GM == GM_FX) {
             const uint32_t ab = v & 0x7fffffffu;          // |v| bits: NaN / inf order last
             if (odd) W.vmB = max(W.vmB, ab); else W.vmA = max(W.vmA, ab);
             // 2^e_l is a power of two: v * sc is exact; v_cvt_i32_f32 saturates
@@ -524,7 +543,7 @@ __device__ __forceinline__ void walk2_issue(Walk2& W, int s, uint32_t cnt,
             const int64_t qw = (int64_t)q * (int64_t)(int32_t)off;
             if (odd) { W.sqB += (int64_t)q; W.swB += (uint64_t)qw; }
             else { W.sqA += (int64_t)q; W.swA += (uint64_t)qw; }
-        } else if (GM == 1) {
+        } else if (GM == GM_INT) {
             // exact: |v * 2^e| < 2^62 for any finite gradient the scale admits
             const float x = rintf(__uint_as_float(v) * G.scale);
             const long long q = (long long)x;
@@ -534,9 +553,9 @@ __device__ __forceinline__ void walk2_issue(Walk2& W, int s, uint32_t cnt,
             W.offB = off;
             W.oldB = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(lo, G.lo, (int)off, 0, 0);
         } else {
-            // fp32 level: still tracked (not GM 5's even streams: the host
+            // fp32 level: still tracked (not GM_BIN_F32's even streams: the host
             // zeroes those levels' scales every step, so their maxima are unused)
-            if (GM == 2 || (BIN && !F32S)) {
+            if (GM == GM_FX || (BIN && !F32S)) {
                 const uint32_t ab = v & 0x7fffffffu;
                 if (odd) W.vmB = max(W.vmB, ab); else W.vmA = max(W.vmA, ab);
             }
@@ -608,7 +627,7 @@ __device__ __forceinline__ void walk2_drain(Walk2& W, uint32_t min_cnt,
 // segment, so an instruction boundary splits them less often; replay of the
 // bench samples, tools/atomic_sim2.py: 15.18 -> 14.65 requests/sample)
 // Ring word 0 of a record: the byte offset 8 (level offset + entry) of its
-// first feature in the grid (GM 4: the entry index within the level, what a
+// first feature in the grid (GM_BIN: the entry index within the level, what a
 // page record holds)
 template <int GM>
 __device__ __forceinline__ void walk2_push(Walk2& W, bool e0, bool e1, uint32_t lvl_off) {
@@ -631,10 +650,10 @@ __device__ __forceinline__ void walk2_push(Walk2& W, bool e0, bool e1, uint32_t 
     // ring; it is overwritten before it is ever read)
     const uint32_t r0 = w2_wrap(W.tail + (e0 ? below : pushed));
     const uint32_t r1 = w2_wrap(W.tail + (e1 ? below + (e0 ? 1u : 0u) : pushed));
-    base[r0] = GM >= 4 ? W.cur0 : 8u * (lvl_off + W.cur0);
+    base[r0] = gm_pages(GM) ? W.cur0 : 8u * (lvl_off + W.cur0);
     base[W2_RING + r0] = __float_as_uint(W.a00);
     base[2 * W2_RING + r0] = __float_as_uint(W.a01);
-    base[r1] = GM >= 4 ? W.cur1 : 8u * (lvl_off + W.cur1);
+    base[r1] = gm_pages(GM) ? W.cur1 : 8u * (lvl_off + W.cur1);
     base[W2_RING + r1] = __float_as_uint(W.a10);
     base[2 * W2_RING + r1] = __float_as_uint(W.a11);
     W.tail = w2_wrap(W.tail + pushed);
@@ -747,7 +766,7 @@ __device__ __forceinline__ void walk2_end(const FieldArgs& a, const LvTab& sT,
     const LvConst lc = walk2_level(a, sT);
     walk2_push<GM>(W, W.ex0 != W2_NONE, W.ex1 != W2_NONE, lc.off);
     walk2_drain<GM>(W, 0u, grad_rs, G, dbg);
-    if (GM == 1) walk2_settle(W, G);
+    if (GM == GM_INT) walk2_settle(W, G);
     walk2_begin(W, W.ring);
 }
 
@@ -1104,10 +1123,13 @@ k_field_bwd(FieldArgs a) {
 //     a per-block global area, reload the weights), then run the MLP backward
 //     over model k's samples of the chunk in 8-tile windows (bwd_window) and
 //     stage dL/dencoding + unit coords as 144-B rows in the block's scratch;
-//  2. walk the chunk's merged order (perm, from rn_bwd_plan) in windows of 256
-//     samples: rows -> LDS (sG/sU) -> grid_scatter_block, unchanged.
-// The grid gradient is the same sum as k_field_bwd's (float atomics: equal up
-// to summation order); dW is identical per model.
+//  2. walk the chunk's merged order (perm, from rn_bwd_plan): each wave walks
+//     two levels over the chunk's eighths in windows of MB_WIN rows, rows ->
+//     LDS -> walk2_window (the row-lane walk above), and drains its rings at
+//     the chunk's end (walk2_end).
+// The grid gradient is the same sum as k_field_bwd's (GM_F32: float atomics,
+// equal up to summation order; the other forms: see GM_*); dW is identical
+// per model.
 // ---------------------------------------------------------------------------
 // scratch row (80 B = 20 floats): dE[32] as f16 in the block iteration's
 // gradient scale (the dX chain's own range; tcnn's dL/dencoding is f16 too) |
@@ -1146,12 +1168,11 @@ __device__ __forceinline__ void dw_unpark(const float* p, f32x16& A, f32x16& B) 
     }
 }
 
-// GM: grid-gradient accumulation. 0 fp32 atomics, 1 exact integer with
-// carries (IntGrad), 2 fixed point for the hashed levels (FxGrad), 3 the
-// fp32 redo of a fixed-point step whose records overflowed the scale (grid
-// scatter of the levels that went in as fixed point only, no dW; the launch
+// GM: grid-gradient accumulation, one of GM_* (next to IntGrad).  GM_FX_REDO
+// is the fp32 redo of a fixed-point or binned step that was flagged (grid
+// scatter of the levels that went in with a scale only, no dW; the launch
 // exits at once unless *F.redo is set).
-// DET = 1 (deterministic mode, with GM 1; an int like GM, the only bool of
+// DET = 1 (deterministic mode, with GM_INT; an int like GM, the only bool of
 // the list stays ABL): chunk c of the plan goes to block
 // c mod gridDim.x, each block takes its chunks in ascending order (no ticket
 // queue), and the block's dW goes with plain stores to its own slot
@@ -1161,13 +1182,14 @@ __device__ __forceinline__ void dw_unpark(const float* p, f32x16& A, f32x16& B) 
 template <int CACHE, bool ABL, int GM, int DET = 0>
 __global__ void __launch_bounds__(BWD_WAVES * 64)
 k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
-    if (GM == 3 && __builtin_nontemporal_load(F.redo) == 0) return;   // uniform: whole grid exits
-    if (GM == 1) {
+    // (uniform: the whole grid exits)
+    if (GM == GM_FX_REDO && __builtin_nontemporal_load(F.redo) == 0) return;
+    if (GM == GM_INT) {
         G.scale = *G.scale_ptr;
         G.lo = rn_rsrc(G.lo_ptr, G.bytes);
         G.carry = rn_rsrc(G.carry_ptr, G.bytes);
     }
-    if (GM == 2) G.fx = rn_rsrc(F.acc, 2 * a.grid_bytes);
+    if (GM == GM_FX) G.fx = rn_rsrc(F.acc, 2 * a.grid_bytes);
     // the walk phase stages its windows over the waves' images AND the
     // weights (the weights are reloaded for the next chunk's MLP phase):
     // eighths 0-3 in sImg (then the rings of waves 4-7), eighths 4-7 in sW.
@@ -1193,7 +1215,7 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
     rn_half* imgX = imgY + RN_IMG_HALFS;
     const __amdgpu_buffer_rsrc_t grad_rs = rn_rsrc(a.grid_grad, 2 * a.grid_bytes);
     const int dbg = ABL ? a.dbg : 0;      // ablation flags (tools/ablate.py) only in ABL builds
-    const bool do_dw = !(rn_dbg(dbg) & 2) && GM != 3;
+    const bool do_dw = !(rn_dbg(dbg) & 2) && GM != GM_FX_REDO;
     // fixed point: this wave's two levels' scales (wave-uniform) and maxima
     float fxA = 0.f, fxB = 0.f;
     uint32_t vmA = 0u, vmB = 0u;
@@ -1201,7 +1223,7 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
     uint64_t swA = 0, swB = 0;
     // binned mode: this wave's open pages (none yet: the first issue takes one)
     uint32_t pgA = 0xffffffffu, pgB = 0xffffffffu, nA = GB_PAGE, nB = GB_PAGE;
-    if (GM >= 2) {
+    if (gm_has_scales(GM)) {
         fxA = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(F.scale[lvA])));
         fxB = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(F.scale[RN_L - 1 - lvA])));
     }
@@ -1515,11 +1537,11 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) atomicAdd(g_rn_cyc + q, (unsigned long long)cyc[q]);
     }
-    if (GM >= 4 && rn_lane() == 0) {             // close this wave's open pages
+    if (gm_pages(GM) && rn_lane() == 0) {        // close this wave's open pages
         if (pgA < G.pool_pages) G.page_meta[pgA] = (uint32_t)lvA | (nA << 8);
         if (pgB < G.pool_pages) G.page_meta[pgB] = (uint32_t)(RN_L - 1 - lvA) | (nB << 8);
     }
-    if (GM == 2 || GM >= 4) {                    // this step's largest |record| per level
+    if (GM == GM_FX || gm_pages(GM)) {           // this step's largest |record| per level
         vmA = rn_wave_max_u32(vmA);
         vmB = rn_wave_max_u32(vmB);
         int64_t dA = sqA, dB = sqB;
@@ -1943,7 +1965,7 @@ k_fx_esum(GridMeta gm, const float* __restrict__ scale, const int32_t* __restric
 // to < 2^27 units.  A level whose largest record reached 2^30 units under the
 // current scale (8x growth since the step the scale came from), or a
 // non-finite one, or whose entries wrapped (entry sum != record sum), sets the
-// redo flag: rn_grid_fx_fold then discards the fixed-point sums and the GM 3
+// redo flag: rn_grid_fx_fold then discards the fixed-point sums and the GM_FX_REDO
 // launch recomputes the grid gradient in fp32.
 // Headroom measured on C3 over 12 Adam steps (tools/fx_diag.py): the largest
 // |entry| of a hashed level stays within 2^1.2 of its largest record, so at
@@ -2523,6 +2545,26 @@ inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
 
 }  // namespace
 
+// The part of FieldArgs every field entry fills alike: the box, the hash-grid
+// level table (offsets/hsize/res/scale: 16 entries each), the f16 grid, the
+// MLP fragments and the ablation flags (after the entry's own checks).
+static void field_args_grid(FieldArgs& a, const void* grid_f16, const uint32_t* level_offset,
+                            const uint32_t* level_hsize, const uint32_t* level_res,
+                            const float* level_scale, const float* xyz_min, const float* extent,
+                            const void* frags) {
+    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
+    a.dbg = rn_dbg(g_field_dbg);
+    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+}
+
+// The same for the compact samples of the K models (ml_compact's segments).
+static void field_args_compact(FieldArgs& a, const float* ts, const int32_t* ray_of,
+                               const float* rays_o, const float* rays_d, const int32_t* seg_base,
+                               const int32_t* seg_count) {
+    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
+    a.seg_base = seg_base; a.seg_count = seg_count;
+}
+
 extern "C" {
 
 void rn_set_debug_flags(int flags) { g_field_dbg = flags; }
@@ -2572,7 +2614,6 @@ int rn_to_f16(const float* src, int64_t n, void* dst, void* stream) {
     return 0;
 }
 
-// hash-grid level table (offsets/hsize/res/scale: 16 entries each)
 int rn_field_fwd(const float* xyzs, const float* dirs, int64_t n_samples, const float* ts,
                  const int32_t* ray_of, const float* rays_o, const float* rays_d,
                  const int32_t* seg_base, const int32_t* seg_count, int32_t n_models,
@@ -2584,10 +2625,9 @@ int rn_field_fwd(const float* xyzs, const float* dirs, int64_t n_samples, const 
     RN_CHECK_ARG(grid_f16 && level_offset && level_hsize && level_res && level_scale && xyz_min &&
                  extent && frags && sigma && rgb, "null pointer");
     FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
+                    frags);
     a.sigma = sigma; a.rgb = rgb; a.feat = (rn_half*)feat_cache;
-    a.dbg = rn_dbg(g_field_dbg);
     dim3 grid(blocks_per_model, n_models);
     if (xyzs) {
         RN_CHECK_ARG(dirs && n_models == 1, "xyz mode needs dirs and a single model");
@@ -2598,8 +2638,7 @@ int rn_field_fwd(const float* xyzs, const float* dirs, int64_t n_samples, const 
     } else {
         RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count,
                      "compact mode needs ts/ray_of/rays/segments");
-        a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-        a.seg_base = seg_base; a.seg_count = seg_count;
+        field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
         if (feat_cache) k_field_fwd<1, CACHE_WRITE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
         else k_field_fwd<1, CACHE_NONE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     }
@@ -2619,9 +2658,8 @@ int rn_field_bwd(const float* xyzs, const float* dirs, int64_t n_samples, const 
     RN_CHECK_ARG(grid_f16 && level_offset && level_hsize && level_res && level_scale && xyz_min &&
                  extent && frags && dL_dsigma && dL_drgb && grid_grad && dw, "null pointer");
     FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.dbg = rn_dbg(g_field_dbg);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
+                    frags);
     a.dsigma = dL_dsigma; a.drgb = dL_drgb; a.grid_grad = grid_grad; a.dw = dw;
     a.feat = (rn_half*)feat_cache;
     dim3 grid(blocks_per_model, n_models);
@@ -2634,8 +2672,7 @@ int rn_field_bwd(const float* xyzs, const float* dirs, int64_t n_samples, const 
     } else {
         RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count,
                      "compact mode needs ts/ray_of/rays/segments");
-        a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-        a.seg_base = seg_base; a.seg_count = seg_count;
+        field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
         if (feat_cache) k_field_bwd<1, CACHE_READ><<<grid, BWD_WAVES * 64, 0, (hipStream_t)stream>>>(a);
         else k_field_bwd<1, CACHE_NONE><<<grid, BWD_WAVES * 64, 0, (hipStream_t)stream>>>(a);
     }
@@ -2683,11 +2720,129 @@ int rn_bwd_plan(const int32_t* counts, const int32_t* offsets, const int32_t* se
     return 0;
 }
 
+}  // extern "C"
+// Launches the k_field_bwd_merged of accumulation form gm.  The instantiations
+// are: the production kernel (ABL false) in every form, GM_F32 and GM_INT with
+// and without the encoding cache (the other forms require it); the ablation
+// kernel (librn_abl.so's timing studies) in the forms but GM_INT and
+// GM_FX_REDO; the deterministic kernel (DET) in GM_INT alone.  The kernels are
+// emitted in the order of their uses here and in field_bwd_merged, and the
+// optimiser's inlining of the functions they share follows that order.
+template <bool ABL, int DET>
+static void launch_bwd_merged(int gm, int blocks, hipStream_t st, const FieldArgs& a,
+                              const MergeArgs& m, const IntGrad& G, const FxGrad& F) {
+#define MB_K(C, M) k_field_bwd_merged<C, ABL, M, DET><<<blocks, BWD_WAVES * 64, 0, st>>>(a, m, G, F)
+    if constexpr (!DET) {
+        if (gm == GM_BIN_F32) MB_K(CACHE_READ, GM_BIN_F32);
+        if (gm == GM_BIN) MB_K(CACHE_READ, GM_BIN);
+        if (gm == GM_FX) MB_K(CACHE_READ, GM_FX);
+        if constexpr (!ABL) if (gm == GM_FX_REDO) MB_K(CACHE_READ, GM_FX_REDO);
+    }
+    if constexpr (!ABL) {
+        if (gm == GM_INT) { if (a.feat) MB_K(CACHE_READ, GM_INT); else MB_K(CACHE_NONE, GM_INT); }
+    }
+    if constexpr (!DET) {
+        if (gm == GM_F32) { if (a.feat) MB_K(CACHE_READ, GM_F32); else MB_K(CACHE_NONE, GM_F32); }
+    }
+#undef MB_K
+}
+
+// The merged backward behind rn_field_bwd_merged and rn_field_bwd_merged_det
+// (who: the entry's name, the prefix of its error texts).  det: the integer
+// form on the static chunk schedule (k_field_bwd_merged DET); dw is then the
+// per-block slots [blocks][K][FIELD_PARAMS], zeroed here (a block writes only
+// the tiles of the models it met), and queue is only read ([1], the chunk
+// count): no ticket to reset.
+static int field_bwd_merged(const char* who, bool det, const float* ts, const int32_t* ray_of,
+                            const float* rays_o, const float* rays_d, const int32_t* seg_base,
+                            const int32_t* seg_count, const int32_t* mstart, const int32_t* perm,
+                            const int32_t* chunk_desc, int32_t* queue, int64_t n_rays,
+                            int32_t n_models, int32_t max_samples, const void* grid_f16,
+                            const uint32_t* level_offset, const uint32_t* level_hsize,
+                            const uint32_t* level_res, const float* level_scale,
+                            const float* xyz_min, const float* extent, const void* frags,
+                            const float* dL_dsigma, const float* dL_drgb, float* grid_grad,
+                            float* dw, const void* feat_cache, float* scratch,
+                            int64_t scratch_rows, float* park, int32_t max_chunk, int32_t blocks,
+                            int32_t* igrad_lo, int32_t* igrad_carry, const float* igrad_scale,
+                            int32_t* fx_acc, const float* fx_scale, uint32_t* fx_stats,
+                            const int32_t* fx_redo, int32_t fx_mode, void* gb_ctl,
+                            uint32_t* gb_page_meta, uint64_t* gb_pages, int32_t gb_pool_pages,
+                            void* stream) {
+#define CHECK(cond, msg) RN_CHECK_ARG_AS(who, cond, msg)
+    CHECK(!igrad_lo || (igrad_carry && igrad_scale), "integer mode needs carry and scale");
+    CHECK(fx_mode >= GM_F32 && fx_mode <= GM_BIN_F32 && fx_mode != GM_INT, "fx_mode: 0, 2, 3, 4 or 5");
+    const bool binned = gm_pages(fx_mode);
+    CHECK(fx_mode != GM_FX || (fx_acc && fx_scale && fx_stats && feat_cache),
+          "fixed-point mode needs acc, scale, stats and the encoding cache");
+    CHECK(!binned || (fx_scale && fx_stats && feat_cache && gb_ctl && gb_page_meta && gb_pages &&
+                      gb_pool_pages >= 1),
+          "binned mode needs scale, stats, the encoding cache and the page pool");
+    for (int l = 0; binned && l < RN_L; ++l)
+        CHECK(level_hsize[l] <= (1u << GB_IDX_BITS) &&
+              level_hsize[l] <= ((uint32_t)GB_MAX_BINS << GB_SLICE_BITS),
+              "binned mode: a level has more than 2^20 entries");
+    CHECK(fx_mode != GM_FX_REDO || (fx_redo && fx_scale && feat_cache),
+          "fixed-point redo needs the redo flag, the step's scales and the encoding cache");
+    CHECK(!(igrad_lo && fx_mode), "integer and fixed-point modes are exclusive");
+    CHECK(n_rays >= 1 && n_models >= 1 && n_models <= MB_KMAX && blocks >= 1 &&
+          max_samples >= 1 && max_chunk >= 1, "bad sizes");
+    CHECK(scratch_rows >= (int64_t)max_chunk + (int64_t)n_models * max_samples,
+          "scratch_rows must be >= max_chunk + n_models * max_samples");
+    CHECK(ts && ray_of && rays_o && rays_d && seg_base && seg_count && mstart && perm &&
+          chunk_desc && queue && grid_f16 && level_offset && level_hsize && level_res &&
+          level_scale && xyz_min && extent && frags && dL_dsigma && dL_drgb && grid_grad && dw &&
+          scratch && park, "null pointer");
+    // fixed point: the wrap checksum's element weights 4 i (fx_weight) stay
+    // injective and below 2^30 up to 2^28 elements
+    CHECK(fx_mode != GM_FX ||
+          2ull * ((uint64_t)level_offset[RN_L - 1] + level_hsize[RN_L - 1]) <= (1ull << 28),
+          "fixed-point mode: the grid has more than 2^28 gradient elements");
+#undef CHECK
+    FieldArgs a{};
+    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
+                    frags);
+    field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
+    a.dsigma = dL_dsigma; a.drgb = dL_drgb; a.grid_grad = grid_grad; a.dw = dw;
+    a.feat = (rn_half*)feat_cache;
+    MergeArgs m{};
+    m.mstart = mstart; m.perm = perm; m.desc = chunk_desc; m.queue = queue; m.scratch = scratch;
+    m.park = park; m.rows_cap = (int)scratch_rows; m.n_rays = (int)n_rays; m.n_models = n_models;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t slots = (size_t)blocks * n_models * FIELD_PARAMS * sizeof(float);
+    if (det) RN_CHECK_HIP_AS(who, hipMemsetAsync(dw, 0, slots, st), "dw_part reset");
+    // the ticket is reset per launch, so a backward can be re-run on one plan
+    else RN_CHECK_HIP_AS(who, hipMemsetAsync(queue, 0, sizeof(int32_t), st), "ticket reset");
+    IntGrad G{};
+    if (igrad_lo) {
+        G.bytes = 2 * a.grid_bytes;            // int32 arrays, same size as the f32 grad
+        G.lo_ptr = igrad_lo; G.carry_ptr = igrad_carry; G.scale_ptr = igrad_scale;
+    }
+    if (binned) {
+        RN_CHECK_HIP_AS(who, hipMemsetAsync(gb_ctl, 0, GB_CTL_RESET_BYTES, st), "page pool reset");
+        G.ctl = (GbCtl*)gb_ctl; G.page_meta = gb_page_meta; G.pages = gb_pages;
+        G.pool_pages = (uint32_t)gb_pool_pages;
+    }
+    FxGrad F{};
+    F.acc = fx_acc; F.scale = fx_scale; F.redo = fx_redo;
+    if (FxStats* S = reinterpret_cast<FxStats*>(fx_stats)) {
+        F.vmax = S->vmax; F.qsum = S->qsum; F.wq = S->wq;
+    }
+    const int gm = fx_mode ? fx_mode : (igrad_lo ? GM_INT : GM_F32);
+    // a timing study's flags select the ablation kernel (librn_abl.so only)
+    const bool abl = RN_ABL && a.dbg && !det && gm != GM_INT && gm != GM_FX_REDO;
+    if (abl) launch_bwd_merged<RN_ABL != 0, 0>(gm, blocks, st, a, m, G, F);
+    else if (!det) launch_bwd_merged<false, 0>(gm, blocks, st, a, m, G, F);
+    else launch_bwd_merged<false, 1>(gm, blocks, st, a, m, G, F);
+    RN_CHECK_LAUNCH_AS(who);
+    return 0;
+}
+
+extern "C" {
 int rn_field_bwd_merged(const float* ts, const int32_t* ray_of, const float* rays_o,
                         const float* rays_d, const int32_t* seg_base, const int32_t* seg_count,
-                        const int32_t* mstart, const int32_t* perm,
-                        const int32_t* chunk_desc, int32_t* queue, int64_t n_rays,
-                        int32_t n_models, int32_t max_samples,
+                        const int32_t* mstart, const int32_t* perm, const int32_t* chunk_desc,
+                        int32_t* queue, int64_t n_rays, int32_t n_models, int32_t max_samples,
                         const void* grid_f16, const uint32_t* level_offset,
                         const uint32_t* level_hsize, const uint32_t* level_res,
                         const float* level_scale, const float* xyz_min, const float* extent,
@@ -2699,107 +2854,15 @@ int rn_field_bwd_merged(const float* ts, const int32_t* ray_of, const float* ray
                         const int32_t* fx_redo, int32_t fx_mode, void* gb_ctl,
                         uint32_t* gb_page_meta, uint64_t* gb_pages, int32_t gb_pool_pages,
                         void* stream) {
-    RN_CHECK_ARG(!igrad_lo || (igrad_carry && igrad_scale), "integer mode needs carry and scale");
-    RN_CHECK_ARG(fx_mode == 0 || fx_mode == 2 || fx_mode == 3 || fx_mode == 4 || fx_mode == 5,
-                 "fx_mode: 0, 2, 3, 4 or 5");
-    const bool binned = fx_mode == 4 || fx_mode == 5;
-    RN_CHECK_ARG(fx_mode != 2 || (fx_acc && fx_scale && fx_stats && feat_cache),
-                 "fixed-point mode needs acc, scale, stats and the encoding cache");
-    RN_CHECK_ARG(!binned || (fx_scale && fx_stats && feat_cache && gb_ctl && gb_page_meta &&
-                                  gb_pages && gb_pool_pages >= 1),
-                 "binned mode needs scale, stats, the encoding cache and the page pool");
-    for (int l = 0; binned && l < RN_L; ++l)
-        RN_CHECK_ARG(level_hsize[l] <= (1u << GB_IDX_BITS) &&
-                     level_hsize[l] <= ((uint32_t)GB_MAX_BINS << GB_SLICE_BITS),
-                     "binned mode: a level has more than 2^20 entries");
-    RN_CHECK_ARG(fx_mode != 3 || (fx_redo && fx_scale && feat_cache),
-                 "fixed-point redo needs the redo flag, the step's scales and the encoding cache");
-    RN_CHECK_ARG(!(igrad_lo && fx_mode), "integer and fixed-point modes are exclusive");
-    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1 && n_models <= MB_KMAX && blocks >= 1 &&
-                 max_samples >= 1 && max_chunk >= 1, "bad sizes");
-    RN_CHECK_ARG(scratch_rows >= (int64_t)max_chunk + (int64_t)n_models * max_samples,
-                 "scratch_rows must be >= max_chunk + n_models * max_samples");
-    RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count && mstart &&
-                 perm && chunk_desc && queue && grid_f16 && level_offset && level_hsize && level_res &&
-                 level_scale && xyz_min && extent && frags && dL_dsigma && dL_drgb && grid_grad &&
-                 dw && scratch && park, "null pointer");
-    // fixed point: the wrap checksum's element weights 4 i (fx_weight) stay
-    // injective and below 2^30 up to 2^28 elements
-    RN_CHECK_ARG(fx_mode != 2 ||
-                 2ull * ((uint64_t)level_offset[RN_L - 1] + level_hsize[RN_L - 1]) <= (1ull << 28),
-                 "fixed-point mode: the grid has more than 2^28 gradient elements");
-    FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.dbg = rn_dbg(g_field_dbg);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
-    a.dsigma = dL_dsigma; a.drgb = dL_drgb; a.grid_grad = grid_grad; a.dw = dw;
-    a.feat = (rn_half*)feat_cache;
-    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-    a.seg_base = seg_base; a.seg_count = seg_count;
-    MergeArgs m{};
-    m.mstart = mstart; m.perm = perm; m.desc = chunk_desc;
-    m.queue = queue;
-    m.scratch = scratch; m.park = park;
-    m.n_rays = (int)n_rays; m.n_models = n_models; m.rows_cap = (int)scratch_rows;
-    hipStream_t st = (hipStream_t)stream;
-    // the ticket is reset per launch, so a backward can be re-run on one plan
-    if (hipMemsetAsync(queue, 0, sizeof(int32_t), st) != hipSuccess) {
-        rn_set_error("%s: ticket reset failed", __func__);
-        return 2;
-    }
-    IntGrad G{};
-    if (igrad_lo) {
-        G.bytes = 2 * a.grid_bytes;            // int32 arrays, same size as the f32 grad
-        G.lo_ptr = igrad_lo; G.carry_ptr = igrad_carry; G.scale_ptr = igrad_scale;
-    }
-    if (binned) {
-        if (hipMemsetAsync(gb_ctl, 0, GB_CTL_RESET_BYTES, st) != hipSuccess) {
-            rn_set_error("%s: page pool reset failed", __func__);
-            return 2;
-        }
-        G.ctl = (GbCtl*)gb_ctl; G.page_meta = gb_page_meta; G.pages = gb_pages;
-        G.pool_pages = (uint32_t)gb_pool_pages;
-    }
-    FxGrad F{};
-    F.acc = fx_acc; F.scale = fx_scale; F.redo = fx_redo;
-    if (fx_stats) {
-        F.vmax = reinterpret_cast<FxStats*>(fx_stats)->vmax;
-        F.qsum = reinterpret_cast<FxStats*>(fx_stats)->qsum;
-        F.wq = reinterpret_cast<FxStats*>(fx_stats)->wq;
-    }
-    const dim3 blk(BWD_WAVES * 64);
-    if constexpr (RN_ABL) {                     // timing studies (librn_abl.so only)
-        if (a.dbg && (binned || fx_mode == 2 || (fx_mode == 0 && !igrad_lo))) {
-            if (fx_mode == 5) k_field_bwd_merged<CACHE_READ, true, 5><<<blocks, blk, 0, st>>>(a, m, G, F);
-            else if (fx_mode == 4) k_field_bwd_merged<CACHE_READ, true, 4><<<blocks, blk, 0, st>>>(a, m, G, F);
-            else if (fx_mode == 2) k_field_bwd_merged<CACHE_READ, true, 2><<<blocks, blk, 0, st>>>(a, m, G, F);
-            else if (feat_cache) k_field_bwd_merged<CACHE_READ, true, 0><<<blocks, blk, 0, st>>>(a, m, G, F);
-            else k_field_bwd_merged<CACHE_NONE, true, 0><<<blocks, blk, 0, st>>>(a, m, G, F);
-            RN_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    if (fx_mode == 5) {
-        k_field_bwd_merged<CACHE_READ, false, 5><<<blocks, blk, 0, st>>>(a, m, G, F);
-    } else if (fx_mode == 4) {
-        k_field_bwd_merged<CACHE_READ, false, 4><<<blocks, blk, 0, st>>>(a, m, G, F);
-    } else if (fx_mode == 2) {
-        k_field_bwd_merged<CACHE_READ, false, 2><<<blocks, blk, 0, st>>>(a, m, G, F);
-    } else if (fx_mode == 3) {
-        k_field_bwd_merged<CACHE_READ, false, 3><<<blocks, blk, 0, st>>>(a, m, G, F);
-    } else if (igrad_lo) {
-        if (feat_cache) k_field_bwd_merged<CACHE_READ, false, 1><<<blocks, blk, 0, st>>>(a, m, G, F);
-        else k_field_bwd_merged<CACHE_NONE, false, 1><<<blocks, blk, 0, st>>>(a, m, G, F);
-    } else {
-        if (feat_cache) k_field_bwd_merged<CACHE_READ, false, 0><<<blocks, blk, 0, st>>>(a, m, G, F);
-        else k_field_bwd_merged<CACHE_NONE, false, 0><<<blocks, blk, 0, st>>>(a, m, G, F);
-    }
-    RN_CHECK_LAUNCH();
-    return 0;
+    return field_bwd_merged(__func__, false, ts, ray_of, rays_o, rays_d, seg_base, seg_count,
+                            mstart, perm, chunk_desc, queue, n_rays, n_models, max_samples,
+                            grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min,
+                            extent, frags, dL_dsigma, dL_drgb, grid_grad, dw, feat_cache, scratch,
+                            scratch_rows, park, max_chunk, blocks, igrad_lo, igrad_carry,
+                            igrad_scale, fx_acc, fx_scale, fx_stats, fx_redo, fx_mode, gb_ctl,
+                            gb_page_meta, gb_pages, gb_pool_pages, stream);
 }
 
-// Deterministic merged backward: the integer-grid kernel on the static chunk
-// schedule, dW into per-block slots (k_field_bwd_merged DET).
 int rn_field_bwd_merged_det(const float* ts, const int32_t* ray_of, const float* rays_o,
                             const float* rays_d, const int32_t* seg_base,
                             const int32_t* seg_count, const int32_t* mstart, const int32_t* perm,
@@ -2816,44 +2879,13 @@ int rn_field_bwd_merged_det(const float* ts, const int32_t* ray_of, const float*
     RN_CHECK_ARG(igrad_lo && igrad_carry && igrad_scale,
                  "the deterministic backward needs igrad_lo, igrad_carry and igrad_scale");
     RN_CHECK_ARG(dw_part, "the deterministic backward needs dw_part");
-    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1 && n_models <= MB_KMAX && blocks >= 1 &&
-                 max_samples >= 1 && max_chunk >= 1, "bad sizes");
-    RN_CHECK_ARG(scratch_rows >= (int64_t)max_chunk + (int64_t)n_models * max_samples,
-                 "scratch_rows must be >= max_chunk + n_models * max_samples");
-    RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count && mstart &&
-                 perm && chunk_desc && queue && grid_f16 && level_offset && level_hsize && level_res &&
-                 level_scale && xyz_min && extent && frags && dL_dsigma && dL_drgb && grid_grad &&
-                 scratch && park, "null pointer");
-    FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
-    a.dsigma = dL_dsigma; a.drgb = dL_drgb; a.grid_grad = grid_grad;
-    a.dw = dw_part;                              // [blocks][K][FIELD_PARAMS]
-    a.feat = (rn_half*)feat_cache;
-    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-    a.seg_base = seg_base; a.seg_count = seg_count;
-    MergeArgs m{};
-    m.mstart = mstart; m.perm = perm; m.desc = chunk_desc;
-    m.queue = const_cast<int32_t*>(queue);       // only [1], the chunk count, is read
-    m.scratch = scratch; m.park = park;
-    m.n_rays = (int)n_rays; m.n_models = n_models; m.rows_cap = (int)scratch_rows;
-    hipStream_t st = (hipStream_t)stream;
-    // a block writes only the tiles of the models it met: everything else of
-    // its slot reads as zero
-    if (hipMemsetAsync(dw_part, 0, (size_t)blocks * n_models * FIELD_PARAMS * sizeof(float), st) !=
-        hipSuccess) {
-        rn_set_error("%s: dw_part reset failed", __func__);
-        return 2;
-    }
-    IntGrad G{};
-    G.bytes = 2 * a.grid_bytes;
-    G.lo_ptr = igrad_lo; G.carry_ptr = igrad_carry; G.scale_ptr = igrad_scale;
-    FxGrad F{};
-    const dim3 blk(BWD_WAVES * 64);
-    if (feat_cache) k_field_bwd_merged<CACHE_READ, false, 1, 1><<<blocks, blk, 0, st>>>(a, m, G, F);
-    else k_field_bwd_merged<CACHE_NONE, false, 1, 1><<<blocks, blk, 0, st>>>(a, m, G, F);
-    RN_CHECK_LAUNCH();
-    return 0;
+    return field_bwd_merged(__func__, true, ts, ray_of, rays_o, rays_d, seg_base, seg_count,
+                            mstart, perm, chunk_desc, const_cast<int32_t*>(queue), n_rays,
+                            n_models, max_samples, grid_f16, level_offset, level_hsize, level_res,
+                            level_scale, xyz_min, extent, frags, dL_dsigma, dL_drgb, grid_grad,
+                            dw_part, feat_cache, scratch, scratch_rows, park, max_chunk, blocks,
+                            igrad_lo, igrad_carry, igrad_scale, nullptr, nullptr, nullptr, nullptr,
+                            GM_F32, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int rn_field_fwd_merged(const float* ts, const int32_t* ray_of, const float* rays_o,
@@ -2874,12 +2906,10 @@ int rn_field_fwd_merged(const float* ts, const int32_t* ray_of, const float* ray
     RN_CHECK_ARG(!(mstart || perm) || (mstart && perm && feat_cache),
                  "merged-order encoding needs mstart, perm and the encoding cache");
     FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.dbg = rn_dbg(g_field_dbg);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
+                    frags);
+    field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
     a.sigma = sigma; a.rgb = rgb; a.feat = (rn_half*)feat_cache;
-    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-    a.seg_base = seg_base; a.seg_count = seg_count;
     MergeArgs m{};
     m.desc = chunk_desc; m.queue = queue;
     m.mstart = mstart; m.perm = perm;
@@ -2887,10 +2917,7 @@ int rn_field_fwd_merged(const float* ts, const int32_t* ray_of, const float* ray
     const bool gw = n_models > FM_LDS_K;
     const size_t lds = gw ? 0 : (size_t)n_models * FIELD_FWD_FRAGS * RN_FRAG_BYTES;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(queue + 2, 0, sizeof(int32_t), st) != hipSuccess) {
-        rn_set_error("%s: ticket reset failed", __func__);
-        return 2;
-    }
+    RN_CHECK_HIP(hipMemsetAsync(queue + 2, 0, sizeof(int32_t), st), "ticket reset");
 #define RN_FM_LAUNCH(C, E)                                                                     \
     do {                                                                                       \
         if (gw) k_field_fwd_merged<C, E, true><<<blocks, threads, 0, st>>>(a, m);              \
@@ -2929,21 +2956,18 @@ int rn_field_fwd_levels(const float* ts, const int32_t* ray_of, const float* ray
                  level_offset && level_hsize && level_res && level_scale && xyz_min && extent &&
                  frags && sigma && rgb && mstart && perm && planes && prep, "null pointer");
     FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.dbg = rn_dbg(g_field_dbg);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
+                    frags);
+    field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
     a.sigma = sigma; a.rgb = rgb; a.feat = (rn_half*)feat_cache;
     a.planes = planes; a.plane_stride = plane_stride;
-    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-    a.seg_base = seg_base; a.seg_count = seg_count;
     MergeArgs m{};
     m.mstart = mstart; m.perm = perm; m.n_rays = (int)n_rays; m.n_models = n_models;
     hipStream_t st = (hipStream_t)stream;
-    if (xq && (hipMemsetAsync(xq, 0, 64 * sizeof(int32_t), st) != hipSuccess ||
-               hipMemsetAsync(xq + 64, 0xff, 16 * sizeof(int32_t), st) != hipSuccess ||
-               hipMemsetAsync(xq + 80, 0, 16 * sizeof(int32_t), st) != hipSuccess)) {
-        rn_set_error("%s: probe reset failed", __func__);
-        return 2;
+    if (xq) {
+        RN_CHECK_HIP(hipMemsetAsync(xq, 0, 64 * sizeof(int32_t), st), "probe reset");
+        RN_CHECK_HIP(hipMemsetAsync(xq + 64, 0xff, 16 * sizeof(int32_t), st), "probe reset");
+        RN_CHECK_HIP(hipMemsetAsync(xq + 80, 0, 16 * sizeof(int32_t), st), "probe reset");
     }
     // (prep_ready: rn_bwd_plan wrote the per-position input as it placed the samples)
     if (!prep_ready) k_enc_prep<<<1024, 256, 0, st>>>(a, m, (float4*)prep);
@@ -2967,10 +2991,7 @@ int rn_seed_scale(const int32_t* seg_base, const int32_t* seg_count, int32_t n_m
     RN_CHECK_ARG(seg_base && seg_count && sigma && dL_dsigma && dL_drgb && work && scale,
                  "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(work, 0, sizeof(uint32_t), st) != hipSuccess) {
-        rn_set_error("%s: memset failed", __func__);
-        return 2;
-    }
+    RN_CHECK_HIP(hipMemsetAsync(work, 0, sizeof(uint32_t), st), "memset");
     k_seed_max<<<dim3(256, n_models), 256, 0, st>>>(seg_base, seg_count, sigma, dL_dsigma,
                                                      dL_drgb, work);
     RN_CHECK_LAUNCH();

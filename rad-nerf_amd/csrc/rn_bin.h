@@ -1,5 +1,5 @@
 // Binned ("store and sum") grid-gradient scatter: the record format and page
-// pool shared by the merged backward's walk (field.hip, GM 4) and the bin /
+// pool shared by the merged backward's walk (field.hip, GM_BIN) and the bin /
 // sum passes (scatter.hip).
 //
 // Why: at scale 16 the merged backward spent 45 % of its time on memory-side
@@ -71,7 +71,7 @@ __host__ __device__ __forceinline__ uint32_t gb_encode(float x) {
     const float y = fminf(fmaxf(rintf(ldexpf(x, -e)), -32768.f), 32768.f);
     return ((uint32_t)(int)y & ((1u << GB_M_BITS) - 1u)) | ((uint32_t)e << GB_M_BITS);
 }
-// The walk's form (field.hip GM 4): the same word for every |x| < 2^46 units
+// The walk's form (field.hip GM_BIN): the same word for every |x| < 2^46 units
 // (there |m| <= 2^15 needs no clamp); a record at or past 2^46, or NaN, sets
 // the redo flag through the level's vmax (k_fx_check), and the step's pages
 // are discarded, so its word need not saturate

@@ -35,21 +35,32 @@ __host__ __device__ constexpr int rn_dbg(int flags) { return RN_ABL ? flags : 0;
 // ---------------------------------------------------------------------------
 extern "C" void rn_set_error(const char* fmt, ...);
 
-#define RN_CHECK_ARG(cond, msg)                                   \
+// (_AS: a helper shared by several entries reports under its caller's name)
+#define RN_CHECK_ARG_AS(who, cond, msg)                           \
     do {                                                          \
-        if (!(cond)) { rn_set_error("%s: %s", __func__, msg);     \
+        if (!(cond)) { rn_set_error("%s: %s", who, msg);          \
                        return 1; }                                \
     } while (0)
+#define RN_CHECK_ARG(cond, msg) RN_CHECK_ARG_AS(__func__, cond, msg)
 
-#define RN_CHECK_LAUNCH()                                                  \
+#define RN_CHECK_LAUNCH_AS(who)                                            \
     do {                                                                   \
         hipError_t _e = hipGetLastError();                                 \
         if (_e != hipSuccess) {                                            \
-            rn_set_error("%s: launch failed: %s", __func__,                \
+            rn_set_error("%s: launch failed: %s", who,                     \
                          hipGetErrorString(_e));                           \
             return 2;                                                      \
         }                                                                  \
     } while (0)
+#define RN_CHECK_LAUNCH() RN_CHECK_LAUNCH_AS(__func__)
+
+// a host-side HIP call (a reset memset) before a launch: status 2 when it fails
+#define RN_CHECK_HIP_AS(who, call, what)                                   \
+    do {                                                                   \
+        if ((call) != hipSuccess) { rn_set_error("%s: %s failed", who, what); \
+                                    return 2; }                            \
+    } while (0)
+#define RN_CHECK_HIP(call, what) RN_CHECK_HIP_AS(__func__, call, what)
 
 // ---------------------------------------------------------------------------
 // reference math helpers (raymarching.cu:7-60, helper_math.h:280-283)

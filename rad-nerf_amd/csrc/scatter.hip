@@ -1,5 +1,5 @@
 // Binned grid-gradient scatter, passes 2 and 3 (the merged backward's walk,
-// field.hip GM 4, is pass 1: it appends each level's records to pages).
+// field.hip GM_BIN, is pass 1: it appends each level's records to pages).
 //
 //   k_grid_bin  one workgroup per page: counting sort of the page's records
 //               by slice of the page's level (gb_slice_bits: 64-4096 entries)

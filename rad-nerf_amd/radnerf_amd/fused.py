@@ -19,11 +19,19 @@ import torch
 
 from . import layout as LY
 from ._lib import lib
+from .networks import field_ptrs, model_bitfields
 
 MAX_SAMPLES = 1024
 NEAR_DISTANCE = 0.01
 SEG_ALIGN = 128
 FX_STATS_BYTES = 640      # include/radnerf.h RN_FX_STATS_BYTES
+# rn_field_bwd_merged's fx_mode, named as csrc/field.hip's GM_*: fp32 atomics
+# (exact integer with the integer triple), fixed point, the fp32 redo of a
+# flagged step, binned, binned with levels 0-7 by fp32 atomics ...
+GM_F32, GM_FX, GM_FX_REDO, GM_BIN, GM_BIN_F32 = 0, 2, 3, 4, 5
+# ... and its tail arguments for a form not in use: the integer triple (lo,
+# carry, scale), the fx tuple (acc, scale, stats, redo, fx_mode), the page pool
+NO_IG, NO_FX, NO_GB = (None, None, None), (None, None, None, None, GM_F32), (None, None, None, 0)
 
 
 # GbCtl (csrc/rn_bin.h) words read back after each binned backward: pool_next
@@ -85,8 +93,15 @@ class Workspace:
         self.perm = torch.empty(cap, **i)
         self.queue = torch.zeros(3, **i)
         self._bwd_scratch = None
-        self._chunks = None
+        self._chunks = self._chunk_desc = None
         self._dist_k = None         # per-segment distortion loss (distortion steps only)
+        # allocated by the first backward that needs them: integer-grid and
+        # fixed-point state (fx_i: the current scale row), the binned scatter's
+        # pool and read-back ring, the deterministic slots, the input gradients
+        self._igrad = self._fx = self._bin = self._bin_ring = None
+        self.fx_i = self._bin_n = 0
+        self.dw_part = self.gate_part = None
+        self.gate_dx = self.dxyz = self.ddir = self.drays_o = self.drays_d = None
         self.generation = 0         # forwards run through this workspace (_MLRenderFn)
 
     @property
@@ -132,7 +147,7 @@ class Workspace:
         records), the per-level statistics block (FX_STATS_BYTES: record
         maxima, plain and weighted record / entry sums; include/radnerf.h)
         and the redo flag."""
-        if getattr(self, "_fx", None) is None or self._fx[0].numel() != n:
+        if self._fx is None or self._fx[0].numel() != n:
             z = dict(device=device, dtype=torch.int32)
             self._fx = (torch.zeros(n, **z), torch.zeros(2, 16, device=device),
                         torch.zeros(FX_STATS_BYTES // 4, **z), torch.zeros(1, **z))
@@ -146,7 +161,7 @@ class Workspace:
         per-page slice runs, per-level page lists (a step that overflows the
         pool is redone in fp32; _bin_pool grows it from the counts the
         backwards read back)."""
-        b = getattr(self, "_bin", None)
+        b = self._bin
         if b is None or b["pages"] < pages:
             lay = lib().bin_layout()
             i = dict(device=self.device, dtype=torch.int32)
@@ -211,8 +226,7 @@ class FusedMLRenderer:
         self.device = device or model.mlp_params.device
         self.ws = Workspace(n_rays, model.size, self.device, capacity=capacity)
         K = model.size
-        bf = [getattr(model, f"density_bitfield_{i}") for i in range(K)]
-        self.bitfield_bytes = bf[0].numel()
+        self.bitfield_bytes = model_bitfields(model)[0].numel()
         self.fwd_blocks = fwd_blocks or max(1, 2048 // K)
         self.bwd_blocks = bwd_blocks or max(1, 256 // K)
         self.feat_cache = True      # field fwd stores the encoding, bwd skips the re-gather
@@ -395,6 +409,11 @@ class FusedMLRenderer:
         # record HIP events around every launch (True) or the named ones (a set)
         self.trace = False
         self.events = {}
+        # set as the chain runs: the plan's parameters and whether it wrote the
+        # level forward's input, the gate's side stream, fx_f32_levels as a tensor
+        self._plan_key = self._side_stream = None
+        self._prep_ready = self._dist_forward = False
+        self._f32_idx = (None, None)
 
     _NO_DET = ("FusedMLRenderer(deterministic=True) needs the merged backward (1 to 8 sub-NeRFs, "
                "merged_bwd on): the per-model backward scatters the grid gradient and dW with "
@@ -427,7 +446,7 @@ class FusedMLRenderer:
         switches as they stand: "binned" (page records, bin + sum passes),
         "fixed-point" (int32 atomics + fold), "int-grad" (exact u32 atomics
         with carries) or "fp32-atomics".  grid_fx / grid_bin / int_grad only
-        act in the merged backward (_field): the per-model backward
+        act in the merged backward (_field_bwd): the per-model backward
         (merged_bwd off, the default above 8 sub-NeRFs) always scatters with
         fp32 atomics, whatever they say."""
         if not self.merged_bwd:
@@ -466,13 +485,13 @@ class FusedMLRenderer:
     def _side(self, dev):
         """Side stream for the gate MLP: it runs beside the march (forward) and
         beside field_bwd (backward), joined back before its outputs are used."""
-        if getattr(self, "_side_stream", None) is None:
+        if self._side_stream is None:
             self._side_stream = torch.cuda.Stream(dev)
         return self._side_stream
 
     def _f32_level_index(self, dev):
         key = (tuple(sorted(int(l) for l in self.fx_f32_levels)), str(dev))
-        if getattr(self, "_f32_idx", (None,))[0] != key:
+        if self._f32_idx[0] != key:
             if any(not 0 <= l < 16 for l in key[0]):
                 raise ValueError(f"fx_f32_levels: hash levels are 0..15, got {key[0]}")
             self._f32_idx = (key, torch.tensor(key[0], dtype=torch.int64, device=dev))
@@ -484,8 +503,7 @@ class FusedMLRenderer:
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in self.events.items()}
 
     def bitfields(self):
-        K = self.model.size
-        bf = [getattr(self.model, f"density_bitfield_{i}") for i in range(K)]
+        bf = model_bitfields(self.model)
         if all(b.data_ptr() == bf[0].data_ptr() + i * self.bitfield_bytes for i, b in enumerate(bf)):
             return bf[0]
         self._bf = torch.stack(bf).contiguous()
@@ -540,7 +558,7 @@ class FusedMLRenderer:
         if self.merged_bwd or self.merged_fwd:
             # the plan also writes the level forward's per-position input
             self._plan(st, rays_o, rays_d if self.level_fwd and self.plan_prep else None)
-        self._field(True, rays_o, rays_d, st)
+        self._field_fwd(rays_o, rays_d, st)
         comp = (w.sigma.data_ptr(), w.rgb.data_ptr(), w.deltas.data_ptr(),
                 w.ts.data_ptr(), w.counts.data_ptr(), w.offsets.data_ptr(), B, K,
                 float(T_threshold), w.used.data_ptr(), w.opacity_k.data_ptr(),
@@ -578,6 +596,14 @@ class FusedMLRenderer:
         """Columns of a (B, G) per-ray tensor that belong to the rendered sub-NeRFs."""
         return x
 
+    def _plan_params(self):
+        """rn_bwd_plan's chunk parameters from the switches as they stand:
+        (max_chunk, min_chunk, head chunks, head size, balance blocks)."""
+        return (self.max_chunk, min(self.min_chunk, self.max_chunk),
+                self.merged_blocks if self.head_chunk else 0,
+                min(self.head_chunk, self.max_chunk),
+                self.merged_blocks if self.balance_chunks else 0)
+
     def _plan(self, st, rays_o=None, rays_d=None):
         """Merged (ray, t) order + chunk schedule of this step's samples
         (rn_bwd_plan), shared by the merged forward and backward; with the
@@ -585,224 +611,203 @@ class FusedMLRenderer:
         per-position input, so rn_field_fwd_levels skips its prep pass."""
         w, L, m = self.ws, lib(), self.model
         prep = w.level_buffers(st)[1] if rays_d is not None else None
-        self._min_chunk = min(self.min_chunk, self.max_chunk)
-        head_n = self.merged_blocks if self.head_chunk else 0
-        head = min(self.head_chunk, self.max_chunk)
-        bal = self.merged_blocks if self.balance_chunks else 0
-        self._cap_chunks, self._chunks = w.chunk_list(self.max_chunk, self._min_chunk, head_n, bal)
+        key = max_chunk, min_chunk, head_n, head, bal = self._plan_params()
+        self._cap_chunks, self._chunks = w.chunk_list(max_chunk, min_chunk, head_n, bal)
         self._ev("bwd_plan", L.bwd_plan, w.counts.data_ptr(), w.offsets.data_ptr(),
                  w.seg_base.data_ptr(), w.seg_count.data_ptr(), w.ts.data_ptr(), w.B, w.K,
-                 head_n, head, self.max_chunk, self._min_chunk, bal, self._cap_chunks,
+                 head_n, head, max_chunk, min_chunk, bal, self._cap_chunks,
                  w.mstart.data_ptr(), w.perm.data_ptr(), self._chunks.data_ptr(),
                  w._chunk_desc.data_ptr(), w.queue.data_ptr(),
-                 None if prep is None else rays_o.data_ptr(),
-                 None if prep is None else rays_d.data_ptr(),
-                 None if prep is None else m._h_min.ctypes.data,
-                 None if prep is None else m._h_ext.ctypes.data,
-                 None if prep is None else prep.data_ptr(), st)
-        self._plan_key = (self.max_chunk, self._min_chunk, head_n, head, bal)
+                 *((None,) * 5 if prep is None else
+                   (rays_o.data_ptr(), rays_d.data_ptr(), m._h_min.ctypes.data,
+                    m._h_ext.ctypes.data, prep.data_ptr())), st)
+        self._plan_key = key
         self._prep_ready = prep is not None
 
-    def _field(self, fwd, rays_o, rays_d, st, grid_grad=None, dw=None):
-        m, w, L = self.model, self.ws, lib()
-        lo, lh, lr, ls = m.xyz_encoder.level_ptrs()
-        common = (None, None, 0, w.ts.data_ptr(), w.ray_of.data_ptr(), rays_o.data_ptr(),
-                  rays_d.data_ptr(), w.seg_base.data_ptr(), w.seg_count.data_ptr(), m.size,
-                  m.xyz_encoder.params_f16().data_ptr(), lo, lh, lr, ls, m._h_min.ctypes.data,
-                  m._h_ext.ctypes.data, m.packed_frags().data_ptr())
-        if fwd and self.level_fwd and (self.merged_bwd or self.merged_fwd):
-            planes, prep = w.level_buffers(st)
-            self._ev("field_fwd", L.field_fwd_levels, w.ts.data_ptr(), w.ray_of.data_ptr(),
-                     rays_o.data_ptr(), rays_d.data_ptr(), w.seg_base.data_ptr(),
-                     w.seg_count.data_ptr(), w.B, m.size, *common[10:], w.sigma.data_ptr(),
-                     w.rgb.data_ptr(), w.feat.data_ptr(), w.mstart.data_ptr(), w.perm.data_ptr(),
-                     planes.data_ptr(), planes.shape[1], prep.data_ptr(),
-                     int(getattr(self, "_prep_ready", False)), self.level_enc_blocks,
-                     self.level_mlp_blocks, None, st)
-            self._prep_ready = False
-        elif fwd and self.merged_fwd:
-            self._ev("field_fwd", L.field_fwd_merged, w.ts.data_ptr(), w.ray_of.data_ptr(),
-                     rays_o.data_ptr(), rays_d.data_ptr(), w.seg_base.data_ptr(),
-                     w.seg_count.data_ptr(), w._chunk_desc.data_ptr(),
-                     w.queue.data_ptr(), w.B, m.size, *common[10:], w.sigma.data_ptr(),
-                     w.rgb.data_ptr(), w.feat.data_ptr() if self.feat_cache else None,
-                     *((w.mstart.data_ptr(), w.perm.data_ptr())
-                       if self.feat_cache and self.merged_encode else (None, None)),
-                     self.merged_fwd_blocks, self.merged_fwd_threads, st)
-        elif fwd:
-            self._ev("field_fwd", L.field_fwd, *common, w.sigma.data_ptr(), w.rgb.data_ptr(),
-                     w.feat.data_ptr() if self.feat_cache else None, self.fwd_blocks, st)
-        elif self.merged_bwd:
-            rows, scratch, park = w.bwd_scratch(self.merged_blocks, self.max_chunk)
-            if getattr(self, "_plan_key", None) != (
-                    self.max_chunk, min(self.min_chunk, self.max_chunk),
-                    self.merged_blocks if self.head_chunk else 0,
-                    min(self.head_chunk, self.max_chunk),
-                    self.merged_blocks if self.balance_chunks else 0):
-                self._plan(st)      # chunk sizes changed since the forward
-            chunks = self._chunks
-            if self.deterministic:
-                self._field_bwd_det(rays_o, rays_d, st, grid_grad, dw, common, rows, scratch, park)
-                return
-            ig = (None, None, None)
-            fx = (None, None, None, None, 0)
-            gb = (None, None, None, 0)
-            use_fx = self.grid_fx and self.feat_cache and not self.int_grad
-            use_bin = use_fx and self.grid_bin
-            if use_fx:
-                acc, scales, stats, redo = w.fx_buffers(grid_grad.numel(), grid_grad.device)
-                cur, nxt = scales[w.fx_i], scales[1 - w.fx_i]
-                if self.fx_f32_levels:
-                    # these levels go in by fp32 atomics this step (a zero
-                    # scale selects the kernel's per-level fp32 path)
-                    cur.index_fill_(0, self._f32_level_index(cur.device), 0.0)
-                n32 = max(0, min(16, int(self.bin_f32_levels))) if use_bin else 0
-                if n32:
-                    cur[:n32].zero_()           # binned mode: coarse levels by fp32 atomics
-                fx = (acc.data_ptr(), cur.data_ptr(), stats.data_ptr(), None, 2)
-            if use_bin:
-                pool = self._bin_pool(w)
-                # fx_mode 5: levels 0-7 (the walk's even streams) are fp32 by
-                # construction, so that walk carries no page code for them
-                fx = (None, cur.data_ptr(), stats.data_ptr(), None, 5 if n32 >= 8 else 4)
-                gb = (pool["ctl"].data_ptr(), pool["meta"].data_ptr(), pool["recs"].data_ptr(),
-                      pool["pages"])
-            if self.int_grad:
-                lo, carry, scale, work = self._igrad_buffers(grid_grad)
-                self._ev("seed_scale", L.seed_scale, w.seg_base.data_ptr(),
-                         w.seg_count.data_ptr(), m.size, w.sigma.data_ptr(), w.dsigma.data_ptr(),
-                         w.drgb.data_ptr(), work.data_ptr(), scale.data_ptr(), st)
-                ig = (lo.data_ptr(), carry.data_ptr(), scale.data_ptr())
-            self._ev("field_bwd", L.field_bwd_merged, w.ts.data_ptr(), w.ray_of.data_ptr(),
-                     rays_o.data_ptr(), rays_d.data_ptr(), w.seg_base.data_ptr(),
-                     w.seg_count.data_ptr(), w.mstart.data_ptr(),
-                     w.perm.data_ptr(), w._chunk_desc.data_ptr(), w.queue.data_ptr(), w.B, m.size,
-                     MAX_SAMPLES,
-                     *common[10:], w.dsigma.data_ptr(), w.drgb.data_ptr(), grid_grad.data_ptr(),
-                     dw.data_ptr(), w.feat.data_ptr() if self.feat_cache else None,
-                     scratch.data_ptr(), rows, park.data_ptr(), self.max_chunk,
-                     self.merged_blocks, *ig, *fx, *gb, st)
-            if self.after_field_bwd is not None:
-                # the MLP gradient (dW) is final here; the grid gradient only
-                # after the fold / bin + sum below: a data-parallel caller
-                # starts the MLP / gate all-reduce now (bench.py)
-                self.after_field_bwd()
-            def fx_redo():
-                # the fp32 redo of a flagged step's grid scatter: exits at once
-                # unless the fold / check set the flag (no host synchronisation)
-                self._ev("fx_redo", L.field_bwd_merged, w.ts.data_ptr(), w.ray_of.data_ptr(),
-                         rays_o.data_ptr(), rays_d.data_ptr(), w.seg_base.data_ptr(),
-                         w.seg_count.data_ptr(), w.mstart.data_ptr(),
-                         w.perm.data_ptr(), w._chunk_desc.data_ptr(), w.queue.data_ptr(), w.B,
-                         m.size, MAX_SAMPLES, *common[10:], w.dsigma.data_ptr(), w.drgb.data_ptr(),
-                         grid_grad.data_ptr(), dw.data_ptr(), w.feat.data_ptr(),
-                         scratch.data_ptr(), rows, park.data_ptr(), self.max_chunk,
-                         self.merged_blocks, None, None, None, None, cur.data_ptr(), None,
-                         redo.data_ptr(), 3, None, None, None, 0, st)
+    def _sample_ptrs(self, rays_o, rays_d):
+        """The six compact-sample arguments of the field entries."""
+        w = self.ws
+        return (w.ts.data_ptr(), w.ray_of.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(),
+                w.seg_base.data_ptr(), w.seg_count.data_ptr())
 
-            if use_bin:
-                # bin the pages and check the step (a record past e5m17's
-                # range, a pool overflow or a refused input flags it for the
-                # fp32 redo), run the redo launch (the sums exit when flagged,
-                # so it can go first), then sum the fine levels, hand them to
-                # after_grid_levels (their all-reduce overlaps the rest) and sum
-                # the coarse levels
-                span = self._ev_open("fx_bin")
-                L.grid_bin_check(lh, pool["ctl"].data_ptr(), pool["meta"].data_ptr(),
-                                 pool["recs"].data_ptr(), pool["recs"].data_ptr(),
-                                 pool["desc"].data_ptr(), pool["lpages"].data_ptr(), pool["pages"],
-                                 cur.data_ptr(), nxt.data_ptr(), stats.data_ptr(),
-                                 redo.data_ptr(), st)
-                self._ev_close(span)
-                # the pages this backward took, read back without a sync
-                # (_bin_pool reads it BIN_LAG backwards later)
-                seen = self._bin_seen(w)
-                # pool_next and the sum passes' sticky fault word (GbCtl)
-                seen[0].copy_(pool["ctl"][:GB_CTL_READ], non_blocking=True)
-                seen[1].record(torch.cuda.current_stream(grid_grad.device))
-                fx_redo()
-                span = self._ev_open("fx_sum")
-                # a split of 16 would hand the whole grid over before any level
-                # is summed (ADVICE r05): the cut lies in [0, 15]
-                split = clamp_split(self.grid_split_level) if self.after_grid_levels else 0
-                sums = ((split, 16), (0, split)) if split > 0 else ((0, 16),)
-                for i, (l0, l1) in enumerate(sums):
-                    L.grid_sum(lo, lh, pool["ctl"].data_ptr(), pool["desc"].data_ptr(),
-                               pool["lpages"].data_ptr(), pool["recs"].data_ptr(), pool["pages"],
-                               cur.data_ptr(), redo.data_ptr(), grid_grad.data_ptr(), l0, l1, st)
-                    if i == 0 and split > 0:
-                        self.after_grid_levels(split)
-                self._ev_close(span)
-                if split == 0 and self.after_grid_levels is not None:
-                    self.after_grid_levels(0)
-                w.fx_i ^= 1
-            elif use_fx:
-                # fold the fixed-point sums into grid_grad (or flag the step for
-                # the fp32 redo), next step's scales; then the redo launch
-                self._ev("fx_fold", L.grid_fx_fold, lo, lh, lr, acc.data_ptr(), cur.data_ptr(),
-                         nxt.data_ptr(), stats.data_ptr(), redo.data_ptr(), grid_grad.data_ptr(),
-                         st)
-                fx_redo()
-                if self.after_grid_levels is not None:
-                    self.after_grid_levels(0)
-                w.fx_i ^= 1
-            if self.int_grad:
-                self._ev("igrad_to_f32", L.igrad_to_f32, grid_grad.numel(), ig[0], ig[1], ig[2],
-                         grid_grad.data_ptr(), st)
-            if not (use_bin or use_fx) and self.after_grid_levels is not None:
-                # fp32 atomics: final after field_bwd (int_grad: after its
-                # conversion into grid_grad, ADVICE r05)
-                self.after_grid_levels(0)
+    def _field(self, fwd, rays_o, rays_d, st, grid_grad=None, dw=None):
+        return (self._field_fwd(rays_o, rays_d, st) if fwd else
+                self._field_bwd(rays_o, rays_d, st, grid_grad, dw))
+
+    def _field_fwd(self, rays_o, rays_d, st):
+        m, w, L = self.model, self.ws, lib()
+        samples, grid = self._sample_ptrs(rays_o, rays_d), field_ptrs(m)
+        out = (w.sigma.data_ptr(), w.rgb.data_ptr())
+        feat = w.feat.data_ptr() if self.feat_cache else None
+        if self.level_fwd and (self.merged_bwd or self.merged_fwd):
+            planes, prep = w.level_buffers(st)
+            self._ev("field_fwd", L.field_fwd_levels, *samples, w.B, m.size, *grid, *out,
+                     w.feat.data_ptr(), w.mstart.data_ptr(), w.perm.data_ptr(),
+                     planes.data_ptr(), planes.shape[1], prep.data_ptr(), int(self._prep_ready),
+                     self.level_enc_blocks, self.level_mlp_blocks, None, st)
+            self._prep_ready = False
+        elif self.merged_fwd:
+            order = ((w.mstart.data_ptr(), w.perm.data_ptr())
+                     if self.feat_cache and self.merged_encode else (None, None))
+            self._ev("field_fwd", L.field_fwd_merged, *samples, w._chunk_desc.data_ptr(),
+                     w.queue.data_ptr(), w.B, m.size, *grid, *out, feat, *order,
+                     self.merged_fwd_blocks, self.merged_fwd_threads, st)
         else:
-            self._ev("field_bwd", L.field_bwd, *common, w.dsigma.data_ptr(),
-                     w.drgb.data_ptr(), grid_grad.data_ptr(), dw.data_ptr(),
-                     w.feat.data_ptr() if self.feat_cache else None, self.bwd_blocks, st)
-            # per-model backward: fp32 atomics only, so the MLP gradient and the
-            # whole grid gradient are final after this one launch
-            if self.after_field_bwd is not None:
-                self.after_field_bwd()
-            if self.after_grid_levels is not None:
-                self.after_grid_levels(0)
+            self._ev("field_fwd", L.field_fwd, None, None, 0, *samples, m.size, *grid, *out, feat,
+                     self.fwd_blocks, st)
+
+    def _field_bwd(self, rays_o, rays_d, st, grid_grad, dw):
+        """One method per form of the grid-gradient scatter (scatter_mode), each
+        from its set-up to its epilogue in stream order.  Each calls
+        after_field_bwd when the MLP gradient (dW) is final -- a data-parallel
+        caller starts the MLP / gate all-reduce there (bench.py) -- and
+        after_grid_levels when the grid gradient (or its fine levels) is."""
+        m, w, L = self.model, self.ws, lib()
+        samples, grid = self._sample_ptrs(rays_o, rays_d), field_ptrs(m)
+        feat = w.feat.data_ptr() if self.feat_cache else None
+        if not self.merged_bwd:         # per-model backward: fp32 atomics only
+            return self._bwd_f32(lambda name: self._ev(
+                name, L.field_bwd, None, None, 0, *samples, m.size, *grid, w.dsigma.data_ptr(),
+                w.drgb.data_ptr(), grid_grad.data_ptr(), dw.data_ptr(), feat, self.bwd_blocks, st))
+        rows, scratch, park = w.bwd_scratch(self.merged_blocks, self.max_chunk)
+        if self._plan_key != self._plan_params():
+            self._plan(st)      # chunk sizes changed since the forward
+        head = (*samples, w.mstart.data_ptr(), w.perm.data_ptr(), w._chunk_desc.data_ptr(),
+                w.queue.data_ptr(), w.B, m.size, MAX_SAMPLES, *grid, w.dsigma.data_ptr(),
+                w.drgb.data_ptr(), grid_grad.data_ptr())
+        tail = (feat, scratch.data_ptr(), rows, park.data_ptr(), self.max_chunk, self.merged_blocks)
+
+        def launch(name, ig=NO_IG, fx=NO_FX, gb=NO_GB, dw_part=None):
+            # (dw_part: the deterministic entry, dW into the per-block slots)
+            if dw_part is not None:
+                self._ev(name, L.field_bwd_merged_det, *head, dw_part.data_ptr(), *tail, *ig, st)
+            else:
+                self._ev(name, L.field_bwd_merged, *head, dw.data_ptr(), *tail, *ig, *fx, *gb, st)
+
+        form = {"int-grad": self._bwd_int, "fixed-point": self._bwd_fx,
+                "binned": self._bwd_binned, "fp32-atomics": self._bwd_f32}[self.scatter_mode]
+        form(launch, grid_grad, dw, st)
+
+    @staticmethod
+    def _hook(fn, *args):
+        if fn is not None:
+            fn(*args)
+
+    def _bwd_f32(self, launch, *_):
+        """fp32 atomics: dW and the whole grid gradient are final after the launch."""
+        launch("field_bwd")
+        self._hook(self.after_field_bwd)
+        self._hook(self.after_grid_levels, 0)
 
     def _igrad_buffers(self, grid_grad):
         """Integer-grid state (rn_seed_scale, rn_igrad_to_f32): lo / carry words
         per gradient element (zero between steps), the step's scale and the
         scale's scratch word."""
         w, n_g = self.ws, grid_grad.numel()
-        if getattr(w, "_igrad", None) is None or w._igrad[0].numel() != n_g:
+        if w._igrad is None or w._igrad[0].numel() != n_g:
             z = dict(device=grid_grad.device, dtype=torch.int32)
             w._igrad = (torch.zeros(n_g, **z), torch.zeros(n_g, **z),
                         torch.ones(1, device=grid_grad.device), torch.zeros(1, **z))
         return w._igrad
 
-    def _field_bwd_det(self, rays_o, rays_d, st, grid_grad, dw, common, rows, scratch, park):
-        """The deterministic merged backward: integer grid sums (order-free),
-        chunk c on block c mod merged_blocks, each block's dW in its own slot
-        of ws.dw_part, the slots added into dw in block order."""
+    def _bwd_int(self, launch, grid_grad, dw, st):
+        """Exact integer grid sums (order-free; int_grad).  Deterministic mode:
+        the same with chunk c on block c mod merged_blocks, each block's dW in
+        its own slot of ws.dw_part, the slots added into dw in block order."""
         m, w, L = self.model, self.ws, lib()
         lo, carry, scale, work = self._igrad_buffers(grid_grad)
-        n_dw = m.size * LY.FIELD_PARAMS
-        if getattr(w, "dw_part", None) is None or w.dw_part.shape != (self.merged_blocks, n_dw):
-            w.dw_part = torch.empty(self.merged_blocks, n_dw, device=grid_grad.device)
+        ig = (lo.data_ptr(), carry.data_ptr(), scale.data_ptr())
+        det, slots = self.deterministic, (self.merged_blocks, m.size * LY.FIELD_PARAMS)
+        if det and (w.dw_part is None or w.dw_part.shape != slots):
+            w.dw_part = torch.empty(*slots, device=grid_grad.device)
         self._ev("seed_scale", L.seed_scale, w.seg_base.data_ptr(), w.seg_count.data_ptr(),
                  m.size, w.sigma.data_ptr(), w.dsigma.data_ptr(), w.drgb.data_ptr(),
                  work.data_ptr(), scale.data_ptr(), st)
-        self._ev("field_bwd", L.field_bwd_merged_det, w.ts.data_ptr(), w.ray_of.data_ptr(),
-                 rays_o.data_ptr(), rays_d.data_ptr(), w.seg_base.data_ptr(),
-                 w.seg_count.data_ptr(), w.mstart.data_ptr(), w.perm.data_ptr(),
-                 w._chunk_desc.data_ptr(), w.queue.data_ptr(), w.B, m.size, MAX_SAMPLES,
-                 *common[10:], w.dsigma.data_ptr(), w.drgb.data_ptr(), grid_grad.data_ptr(),
-                 w.dw_part.data_ptr(), w.feat.data_ptr() if self.feat_cache else None,
-                 scratch.data_ptr(), rows, park.data_ptr(), self.max_chunk, self.merged_blocks,
-                 lo.data_ptr(), carry.data_ptr(), scale.data_ptr(), st)
-        self._ev("dw_reduce", L.reduce_partials, w.dw_part.data_ptr(), self.merged_blocks, n_dw,
-                 dw.data_ptr(), st)
-        if self.after_field_bwd is not None:
-            self.after_field_bwd()          # the MLP gradient is final here
-        self._ev("igrad_to_f32", L.igrad_to_f32, grid_grad.numel(), lo.data_ptr(),
-                 carry.data_ptr(), scale.data_ptr(), grid_grad.data_ptr(), st)
-        if self.after_grid_levels is not None:
-            self.after_grid_levels(0)
+        launch("field_bwd", ig=ig, dw_part=w.dw_part if det else None)
+        if det:
+            self._ev("dw_reduce", L.reduce_partials, w.dw_part.data_ptr(), *slots, dw.data_ptr(),
+                     st)
+        self._hook(self.after_field_bwd)
+        # the grid gradient is final after its conversion into grid_grad (ADVICE r05)
+        self._ev("igrad_to_f32", L.igrad_to_f32, grid_grad.numel(), *ig, grid_grad.data_ptr(), st)
+        self._hook(self.after_grid_levels, 0)
+
+    def _fx_state(self, grid_grad, n32=0):
+        """This step's fixed-point state (ws.fx_buffers; cur / nxt: the current
+        and next scale rows).  fx_f32_levels and the binned form's coarse levels
+        [0, n32) go in by fp32 atomics this step (a zero scale selects the
+        kernel's per-level fp32 path)."""
+        w = self.ws
+        acc, scales, stats, redo = w.fx_buffers(grid_grad.numel(), grid_grad.device)
+        cur, nxt = scales[w.fx_i], scales[1 - w.fx_i]
+        if self.fx_f32_levels:
+            cur.index_fill_(0, self._f32_level_index(cur.device), 0.0)
+        if n32:
+            cur[:n32].zero_()
+        return acc, cur, nxt, stats, redo
+
+    def _bwd_fx(self, launch, grid_grad, dw, st):
+        """Fixed point (int32 atomics): the launch, the fold of the sums into
+        grid_grad (or the flag for the fp32 redo) with the next step's scales,
+        the redo launch."""
+        w, L = self.ws, lib()
+        lo, lh, lr, _ = self.model.xyz_encoder.level_ptrs()
+        acc, cur, nxt, stats, redo = self._fx_state(grid_grad)
+        launch("field_bwd", fx=(acc.data_ptr(), cur.data_ptr(), stats.data_ptr(), None, GM_FX))
+        self._hook(self.after_field_bwd)
+        self._ev("fx_fold", L.grid_fx_fold, lo, lh, lr, acc.data_ptr(), cur.data_ptr(),
+                 nxt.data_ptr(), stats.data_ptr(), redo.data_ptr(), grid_grad.data_ptr(), st)
+        # the fp32 redo of a flagged step's grid scatter: exits at once unless
+        # the fold / check set the flag (no host synchronisation)
+        launch("fx_redo", fx=(None, cur.data_ptr(), None, redo.data_ptr(), GM_FX_REDO))
+        self._hook(self.after_grid_levels, 0)
+        w.fx_i ^= 1
+
+    def _bwd_binned(self, launch, grid_grad, dw, st):
+        """Binned: the walk appends page records; bin the pages and check the
+        step (a record past e5m17's range, a pool overflow or a refused input
+        flags it for the fp32 redo), run the redo launch (the sums exit when
+        flagged, so it can go first), then sum the fine levels, hand them to
+        after_grid_levels (their all-reduce overlaps the rest) and sum the
+        coarse levels."""
+        w, L = self.ws, lib()
+        lo, lh, _, _ = self.model.xyz_encoder.level_ptrs()
+        n32 = max(0, min(16, int(self.bin_f32_levels)))
+        acc, cur, nxt, stats, redo = self._fx_state(grid_grad, n32)
+        pool = self._bin_pool(w)
+        ctl, meta, recs, desc, lpages = (pool[k].data_ptr() for k in
+                                         ("ctl", "meta", "recs", "desc", "lpages"))
+        # GM_BIN_F32: levels 0-7 (the walk's even streams) are fp32 by
+        # construction, so that walk carries no page code for them
+        launch("field_bwd", fx=(None, cur.data_ptr(), stats.data_ptr(), None,
+                                GM_BIN_F32 if n32 >= 8 else GM_BIN),
+               gb=(ctl, meta, recs, pool["pages"]))
+        self._hook(self.after_field_bwd)
+        span = self._ev_open("fx_bin")
+        L.grid_bin_check(lh, ctl, meta, recs, recs, desc, lpages, pool["pages"], cur.data_ptr(),
+                         nxt.data_ptr(), stats.data_ptr(), redo.data_ptr(), st)
+        self._ev_close(span)
+        # the pages this backward took, read back without a sync (_bin_pool
+        # reads it BIN_LAG backwards later): pool_next and the sum passes'
+        # sticky fault word (GbCtl)
+        seen = self._bin_seen(w)
+        seen[0].copy_(pool["ctl"][:GB_CTL_READ], non_blocking=True)
+        seen[1].record(torch.cuda.current_stream(grid_grad.device))
+        launch("fx_redo", fx=(None, cur.data_ptr(), None, redo.data_ptr(), GM_FX_REDO))
+        span = self._ev_open("fx_sum")
+        # a split of 16 would hand the whole grid over before any level
+        # is summed (ADVICE r05): the cut lies in [0, 15]
+        split = clamp_split(self.grid_split_level) if self.after_grid_levels else 0
+        sums = ((split, 16), (0, split)) if split > 0 else ((0, 16),)
+        for i, (l0, l1) in enumerate(sums):
+            L.grid_sum(lo, lh, ctl, desc, lpages, recs, pool["pages"], cur.data_ptr(),
+                       redo.data_ptr(), grid_grad.data_ptr(), l0, l1, st)
+            if i == 0 and split > 0:
+                self.after_grid_levels(split)
+        self._ev_close(span)
+        if split == 0:
+            self._hook(self.after_grid_levels, 0)
+        w.fx_i ^= 1
 
     # pool growth reads the page count of the binned backward this many
     # backwards back, waiting for it if needed (ADVICE r04: reading whichever
@@ -812,11 +817,10 @@ class FusedMLRenderer:
 
     def _bin_seen(self, w):
         """the next of BIN_LAG + 1 pinned (count, event) slots, in turn"""
-        ring = getattr(w, "_bin_ring", None)
+        ring = w._bin_ring
         if ring is None:
             ring = w._bin_ring = [[torch.zeros(GB_CTL_READ, dtype=torch.int32, pin_memory=True),
                                    None, -1] for _ in range(self.BIN_LAG + 1)]
-            w._bin_n = 0
         slot = ring[w._bin_n % len(ring)]
         slot[1] = torch.cuda.Event()
         slot[2] = w._bin_n
@@ -830,7 +834,7 @@ class FusedMLRenderer:
         asynchronously, is waited for here: a function of the step sequence,
         not of how far the host runs ahead)."""
         lay = lib().bin_layout()
-        b = getattr(w, "_bin", None)
+        b = w._bin
         if b is None:
             # every wave keeps one page per level open (2 per wave of each
             # persistent block), so a step fills pages only partly at small sizes
@@ -838,8 +842,7 @@ class FusedMLRenderer:
                     2 * 8 * self.merged_blocks)
         else:
             need = b["pages"]
-            ring = getattr(w, "_bin_ring", None)
-            n = getattr(w, "_bin_n", 0) - self.BIN_LAG
+            ring, n = w._bin_ring, w._bin_n - self.BIN_LAG
             if ring is not None and n >= 0:
                 slot = ring[n % len(ring)]
                 if slot[2] == n and slot[1] is not None:
@@ -898,7 +901,7 @@ class FusedMLRenderer:
                 # one wave per block into the block's slot of ws.gate_part, the
                 # slots added into gate_grad in block order, on the gate's stream
                 n_par = gate_grad.numel()
-                if getattr(w, "gate_part", None) is None or w.gate_part.shape != (n_blk, n_par):
+                if w.gate_part is None or w.gate_part.shape != (n_blk, n_par):
                     w.gate_part = torch.empty(n_blk, n_par, device=dev)
                 self._ev("gate_bwd", L.gate_bwd_det, rays_o.data_ptr(), gate_in2.data_ptr(), 3,
                          B, G, frags.data_ptr(), dgate.data_ptr(), w.gate_part.data_ptr(), n_par,
@@ -929,7 +932,7 @@ class FusedMLRenderer:
                      w.rgb_k.data_ptr(), B, K, float(T_threshold), w.dsigma.data_ptr(),
                      w.drgb.data_ptr(), st)
         else:
-            if not getattr(self, "_dist_forward", False):
+            if not self._dist_forward:
                 raise RuntimeError("backward(dL_ddist=...): the forward of this step ran "
                                    "without distortion=True")
             seed = torch.is_tensor(dL_ddist)
@@ -948,7 +951,7 @@ class FusedMLRenderer:
             gate_bwd(side)
         elif gate_at == "main":         # in line, before field_bwd
             gate_bwd(main)
-        self._field(False, rays_o, rays_d, st, grid_grad, mlp_grad)
+        self._field_bwd(rays_o, rays_d, st, grid_grad, mlp_grad)
         if self.input_grad:
             self._input_grads(rays_o, rays_d, st)
         if gate_at in ("early", "field"):
@@ -960,7 +963,7 @@ class FusedMLRenderer:
 
     def _gate_dinput(self, B, dev):
         w = self.ws
-        if getattr(w, "gate_dx", None) is None or w.gate_dx.shape[0] != B:
+        if w.gate_dx is None or w.gate_dx.shape[0] != B:
             w.gate_dx = torch.empty(B, 6, device=dev)
         return w.gate_dx
 
@@ -971,17 +974,13 @@ class FusedMLRenderer:
         ray's samples (custom_functions.py:102-112).  The gate's own input
         gradient is in ws.gate_dx ((B, 6): rays_o | second gate input)."""
         m, w, L = self.model, self.ws, lib()
-        if getattr(w, "dxyz", None) is None:
+        if w.dxyz is None:
             w.dxyz = torch.empty(w.capacity, 3, device=w.device)
             w.ddir = torch.empty(w.capacity, 3, device=w.device)
             w.drays_o = torch.empty(w.B, 3, device=w.device)
             w.drays_d = torch.empty(w.B, 3, device=w.device)
-        lo, lh, lr, ls = m.xyz_encoder.level_ptrs()
-        self._ev("field_dinput", L.field_dinput, None, None, 0, w.ts.data_ptr(),
-                 w.ray_of.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(),
-                 w.seg_base.data_ptr(), w.seg_count.data_ptr(), m.size,
-                 m.xyz_encoder.params_f16().data_ptr(), lo, lh, lr, ls, m._h_min.ctypes.data,
-                 m._h_ext.ctypes.data, m.packed_frags().data_ptr(),
+        self._ev("field_dinput", L.field_dinput, None, None, 0,
+                 *self._sample_ptrs(rays_o, rays_d), m.size, *field_ptrs(m),
                  m.packed_dinput_frags().data_ptr(), w.dsigma.data_ptr(), w.drgb.data_ptr(),
                  w.feat.data_ptr() if self.feat_cache else None, w.dxyz.data_ptr(),
                  w.ddir.data_ptr(), self.fwd_blocks, st)

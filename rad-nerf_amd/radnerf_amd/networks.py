@@ -102,6 +102,23 @@ def _param_key(p):
     return (p._version, getattr(p, "_rn_epoch", 0))
 
 
+def field_ptrs(model, ind=None):
+    """The eight grid / weights arguments every field entry of librn takes, in
+    the C order: the f16 grid, the level table (offset, hsize, res, scale), the
+    box's min and extent (host arrays) and the packed MLP fragments -- of
+    sub-NeRF `ind` alone, or (None) of every sub-NeRF of `model` (an MNGP or a
+    view of one, pinned.ModelSlice)."""
+    grid16, frags = model.xyz_encoder.params_f16(), model.packed_frags()
+    return (grid16.data_ptr(), *model.xyz_encoder.level_ptrs(), model._h_min.ctypes.data,
+            model._h_ext.ctypes.data,
+            frags.data_ptr() + (0 if ind is None else ind * frags.shape[1] * 2))
+
+
+def model_bitfields(model):
+    """The occupancy bitfields of the model's sub-NeRFs, in order."""
+    return [getattr(model, f"density_bitfield_{i}") for i in range(model.size)]
+
+
 class _FieldFn(torch.autograd.Function):
     """MNGP.forward(x, d, ind) on rn_field_fwd / rn_field_bwd."""
 
@@ -275,16 +292,11 @@ class MNGP(nn.Module):
 
     def _launch_dinput(self, xyzs, dirs, ind, dsigma, drgb, dxyz, ddir, feat=None):
         """dL/dxyzs, dL/ddirs of forward(xyzs, dirs, ind) (rn_field_dinput)."""
-        frags = self.packed_frags()
         dfr = self.packed_dinput_frags()
-        grid16 = self.xyz_encoder.params_f16()
-        lo, lh, lr, ls = self.xyz_encoder.level_ptrs()
         n = xyzs.shape[0]
         nb = max(1, min(2048, (n + 127) // 128))
         lib().field_dinput(xyzs.data_ptr(), dirs.data_ptr(), n, None, None, None, None, None, None,
-                           1, grid16.data_ptr(), lo, lh, lr, ls, self._h_min.ctypes.data,
-                           self._h_ext.ctypes.data,
-                           frags.data_ptr() + ind * frags.shape[1] * 2,
+                           1, *field_ptrs(self, ind),
                            dfr.data_ptr() + ind * dfr.shape[1] * 2, dsigma.data_ptr(),
                            drgb.data_ptr(), None if feat is None else feat.data_ptr(),
                            dxyz.data_ptr(), ddir.data_ptr(), nb, _stream(xyzs.device))
@@ -292,22 +304,17 @@ class MNGP(nn.Module):
     def _launch_field(self, fwd, xyzs, dirs, ind, sigma=None, rgb=None, dsigma=None, drgb=None,
                       grid_grad=None, dw=None, blocks=None, feat=None):
         dev = xyzs.device
-        frags = self.packed_frags()
-        grid16 = self.xyz_encoder.params_f16()
-        fptr = frags.data_ptr() + ind * frags.shape[1] * 2
-        lo, lh, lr, ls = self.xyz_encoder.level_ptrs()
+        grid = field_ptrs(self, ind)
         n = xyzs.shape[0]
         if fwd:
             nb = blocks or max(1, min(2048, (n + 127) // 128))
             lib().field_fwd(xyzs.data_ptr(), dirs.data_ptr(), n, None, None, None, None, None,
-                            None, 1, grid16.data_ptr(), lo, lh, lr, ls, self._h_min.ctypes.data,
-                            self._h_ext.ctypes.data, fptr, sigma.data_ptr(), rgb.data_ptr(),
+                            None, 1, *grid, sigma.data_ptr(), rgb.data_ptr(),
                             None if feat is None else feat.data_ptr(), nb, _stream(dev))
         else:
             nb = blocks or max(1, min(256, (n + 255) // 256))
             lib().field_bwd(xyzs.data_ptr(), dirs.data_ptr(), n, None, None, None, None, None,
-                            None, 1, grid16.data_ptr(), lo, lh, lr, ls, self._h_min.ctypes.data,
-                            self._h_ext.ctypes.data, fptr, dsigma.data_ptr(), drgb.data_ptr(),
+                            None, 1, *grid, dsigma.data_ptr(), drgb.data_ptr(),
                             grid_grad.data_ptr(), dw.data_ptr() + ind * LY.FIELD_PARAMS * 4,
                             None if feat is None else feat.data_ptr(), nb, _stream(dev))
 
@@ -321,11 +328,7 @@ class MNGP(nn.Module):
         return (sigma, feat) if return_feat else sigma
 
     def _launch_density(self, x, ind, sigma, feat):
-        frags = self.packed_frags()
-        lo, lh, lr, ls = self.xyz_encoder.level_ptrs()
-        lib().field_density(x.data_ptr(), x.shape[0], self.xyz_encoder.params_f16().data_ptr(),
-                            lo, lh, lr, ls, self._h_min.ctypes.data, self._h_ext.ctypes.data,
-                            frags.data_ptr() + ind * frags.shape[1] * 2, sigma.data_ptr(),
+        lib().field_density(x.data_ptr(), x.shape[0], *field_ptrs(self, ind), sigma.data_ptr(),
                             None if feat is None else feat.data_ptr(), _stream(x.device))
 
     def forward(self, x, d, ind, **kwargs):
@@ -391,7 +394,7 @@ class MNGP(nn.Module):
         K, C, G = self.size, self.cascades, self.grid_size
         dev = self.mlp_params.device
         grids = [getattr(self, f"density_grid_{i}") for i in range(K)]
-        bits = [getattr(self, f"density_bitfield_{i}") for i in range(K)]
+        bits = model_bitfields(self)
         for i, g in enumerate(grids):
             if not (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == C * G ** 3):
                 g = g.float().contiguous()
@@ -471,11 +474,9 @@ class MNGP(nn.Module):
                   "thr": torch.empty(K, device=dev)}
             self._du = du
         ptrs = self._grid_ptrs()
-        lo, lh, lr, ls = self.xyz_encoder.level_ptrs()
         args = (ptrs.data_ptr(), ptrs.data_ptr() + 8 * K, K, C, G, float(self.scale),
                 float(density_threshold), float(decay), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                self.xyz_encoder.params_f16().data_ptr(), lo, lh, lr, ls, self._h_min.ctypes.data,
-                self._h_ext.ctypes.data, self.packed_frags().data_ptr(), du["tmp"].data_ptr(),
+                *field_ptrs(self), du["tmp"].data_ptr(),
                 du["occ"].data_ptr(), du["blk"].data_ptr(), du["part"].data_ptr(),
                 du["thr"].data_ptr(), int(bool(all_cells)))
         count = getattr(self, "count_grid", None)
