@@ -478,8 +478,6 @@ k_distortion_bw(int n_rows, const float* __restrict__ dL_dloss,
     }
 }
 
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
-
 }  // namespace
 
 extern "C" {

@@ -1,5 +1,6 @@
 // Fused Rad-NeRF field for gfx950: shared multiresolution hash grid + per
-// sub-NeRF geo/rgb MLPs, forward and backward.
+// sub-NeRF geo/rgb MLPs.  This file: the per-model (drop-in) forward and
+// backward, and the merged backward of the fused path.
 //
 // Reference (behaviour): models/networks.py:291-328 (MNGP.density/forward),
 // :229-289 (tcnn Grid/Hash encoding L=16 F=2 T=2^19 N_min=16, SH degree 4,
@@ -16,23 +17,30 @@
 // Kernels:
 //  * k_field_fwd / k_field_bwd: one sub-NeRF per blockIdx.y (the drop-in
 //    path, one model at a time like the reference).
-//  * k_bwd_plan + k_bwd_chunks: merged (ray, t) order of the K models'
-//    samples and a chunk schedule of whole rays.
-//  * k_field_fwd_merged: the K models' tiles of a chunk interleaved on one
-//    CU (their corners share L1 lines).
 //  * k_field_bwd_merged: per chunk, the MLP backward model by model, then the
 //    hash-grid gradient of all K models scattered in merged per-ray order
 //    (row-lane walk + per-stream rings of fp32 atomics; optionally exact
 //    integer accumulation).
+//  * k_pack_f16 / k_to_f16: the f16 packers of the table and the fragments.
 // Backward MLP: recompute the forward from the encoding cache, run the dX
 // chain on MFMA, and form dW = dY . X^T block-cooperatively from sample-major
 // LDS images (MFMA again), held in registers across windows.
+// The two backward kernels share bwd_window and the dW tiles, and they stay in
+// one file because of it: compiled in separate units, every kernel that
+// flushes dW with atomics came out with other instructions, whatever the
+// order of the declarations (the trials: profiles/fieldsplit/device_code.txt).
+// The rest of the fused path: field_plan.hip (merged order and chunk schedule),
+// field_fwd_merged.hip (merged and level-partitioned forwards), field_grad.hip
+// (epilogues of the grid-gradient forms, rn_gradform.h); input gradients and
+// the density-only evaluation: field_aux.hip.  The ablation flags of all of
+// them (rn_set_debug_flags) are kept here.
 #include "rn_field.h"
 #include "rn_bin.h"
+#include "rn_merge.h"
+#include "rn_gradform.h"
 #pragma clang fp contract(off)
 
 static int g_field_dbg = 0;
-static uint64_t g_level_pairing = 0;     // rn_field_fwd_levels' level groups (0 = default)
 // ablation builds only (flag 4096): per-phase wave cycles of the merged
 // backward, summed over waves (s_memtime): [0] MLP phase, [1] walk staging
 // (row loads + LDS fill, up to the barrier), [2] walks, [3] chunk tails
@@ -330,42 +338,6 @@ __device__ __forceinline__ void walk2_begin(Walk2& W, uint32_t* ring) {
     W.started = false;
 }
 
-// How the merged backward accumulates the grid gradient: k_field_bwd_merged's
-// and the walk's GM template argument.  rn_field_bwd_merged's public fx_mode
-// takes the same values (0 and 2-5; GM_INT is selected by igrad_lo), and
-// fused.py names them alike.
-enum : int {
-    GM_F32 = 0,        // fp32 atomics
-    GM_INT = 1,        // exact integer with carries (IntGrad)
-    GM_FX = 2,         // fixed point for the levels with a scale (FxGrad)
-    GM_FX_REDO = 3,    // fp32 redo of a flagged fixed-point / binned step
-    GM_BIN = 4,        // binned: page records (rn_bin.h)
-    GM_BIN_F32 = 5,    // binned, the even streams' levels (0-7) by fp32 atomics
-};
-// has per-level scales (FxGrad::scale; a zero scale = fp32 atomics for the level)
-constexpr bool gm_has_scales(int gm) { return gm >= GM_FX; }
-// appends page records to the pool instead of issuing atomics
-constexpr bool gm_pages(int gm) { return gm == GM_BIN || gm == GM_BIN_F32; }
-// the even streams are fp32 at compile time (no page code for them)
-constexpr bool gm_even_f32(int gm) { return gm == GM_BIN_F32; }
-
-// Exact integer accumulation of the grid gradient (IG mode).  Each record
-// value v becomes q = rint(v * 2^scale_exp) (int64), added as a 32-bit low
-// word with a returning atomic; the high word plus any signed overflow of the
-// low word (read from the returned old value) goes to a parallel carry array,
-// so every entry holds carry * 2^32 + low exactly: sums are order-independent
-// (bitwise reproducible) and u32 atomics run 28 % faster than f32 at the
-// memory side (profiles/r01/atomic_probe.json).  A carry add is rare.
-struct IntGrad {
-    __amdgpu_buffer_rsrc_t lo, carry;   // int32 [entries][2] each (built in the kernel)
-    float scale;                        // 2^scale_exp (loaded from scale_ptr)
-    int32_t* lo_ptr; int32_t* carry_ptr; const float* scale_ptr;
-    uint32_t bytes;
-    __amdgpu_buffer_rsrc_t fx;          // fixed-point mode (GM_FX): FxGrad::acc
-    // binned mode (GM_BIN, rn_bin.h): the page pool the walk appends to
-    GbCtl* ctl; uint32_t* page_meta; uint64_t* pages; uint32_t pool_pages;
-};
-
 __device__ __forceinline__ void ig_check(int32_t old, int32_t lo, int32_t hi, uint32_t off,
                                          const IntGrad& G) {
     const int32_t nw = (int32_t)((uint32_t)old + (uint32_t)lo);
@@ -373,62 +345,6 @@ __device__ __forceinline__ void ig_check(int32_t old, int32_t lo, int32_t hi, ui
     const int32_t c = hi + (ov ? (lo > 0 ? 1 : -1) : 0);
     if (c != 0) __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(c, G.carry, (int)off, 0, 0);
 }
-
-// Fixed-point accumulation of the hashed levels' grid gradient (GM_FX, the
-// default of the merged backward).  A record v of level l is added as the
-// int32 rint(v * 2^e_l) with a NON-returning u32 atomic into `acc` (same
-// layout as grid_grad): the memory side serves u32 adds at 26.6 G requests/s
-// against 20.9 for f32 (profiles/r01/atomic_probe.json), and the sums are
-// exact, so these levels' gradients are bitwise reproducible.  e_l comes from
-// the previous step's largest record of the level (rn_grid_fx_fold): that
-// record maps to < 2^27 units (2^23 until round 6; FX_TARGET_BITS below),
-// leaving 2^4 max-size records of headroom per entry (an entry of a hashed
-// level takes ~77 records per C3 step, of mixed sign, and its largest sum
-// stays within 2^1.2 of the largest record).  The kernel records this step's
-// largest |record| per level; when it reaches 2^30 units (8x growth) or is not
-// finite, rn_grid_fx_fold discards the fixed-point sums and the GM_FX_REDO launch
-// redoes the grid scatter in fp32.
-// The first step of a workspace (scale 0) uses fp32 atomics and measures the
-// records; the dense levels (few requests, but entries that sum hundreds of
-// records) go fixed point from then on with a scale capped by their largest
-// entry (k_fx_check).
-// An int32 entry can still wrap with every record under 2^30 units (many
-// same-sign records on one entry); the kernel therefore also sums each
-// level's integer records exactly (int64), and rn_grid_fx_fold sums the
-// level's int32 entries exactly: a wrapped entry makes the two differ by a
-// multiple of 2^32, which sets the redo flag too.  (A float sum of the
-// records is not enough: its rounding reached 2^31 on trained grids.)
-struct FxStats {           // rn_grid_fx_fold / rn_field_bwd_merged fx_stats block
-    uint32_t vmax[RN_L];   // largest |record| this step (float bits, atomicMax)
-    uint32_t emax[RN_L];   // largest |entry| this step, gradient units (float bits; rn_grid_fx_fold)
-    int64_t qsum[RN_L];    // sum of the issued integer records
-    int64_t esum[RN_L];    // sum of the int32 entries (rn_grid_fx_fold)
-    uint64_t wq[RN_L];     // sum of record * fx_weight(element), mod 2^64
-    uint64_t we[RN_L];     // sum of entry * fx_weight(element), mod 2^64 (rn_grid_fx_fold)
-};
-static_assert(sizeof(FxStats) == RN_FX_STATS_BYTES, "FxStats layout (include/radnerf.h)");
-
-// weight of grid-gradient element i (an int32 of the fixed-point table) in the
-// position-weighted checksums: its byte offset 4 i, which the walk's issue
-// already holds (no multiply on the issue path).  Wraps of +-2^32 on two
-// different elements a, b move the weighted sum by 2^34 (a - b) mod 2^64,
-// which is 0 only for a = b mod 2^30: never on a table of at most 2^28
-// elements (rn_field_bwd_merged refuses fixed point for larger ones).  (Any
-// injective weight is linear in the same way for three or more wraps: round
-// 5's odd multiplier, (i mod 2^24) * 0x9E3779, cancelled exactly when
-// sum(+-i) = 0 mod 2^32, like this one.)  The weights are < 2^30, so the
-// walk adds q * w with one signed 32 x 32 -> 64 mad.
-__host__ __device__ __forceinline__ uint32_t fx_weight(uint32_t i) { return 4u * i; }
-
-struct FxGrad {
-    int32_t* acc;              // int32 [entries][2]
-    const float* scale;        // [RN_L] 2^e_l, 0 = fp32 atomics for the level
-    uint32_t* vmax;            // FxStats::vmax
-    int64_t* qsum;             // FxStats::qsum
-    uint64_t* wq;              // FxStats::wq
-    const int32_t* redo;       // GM_FX_REDO: the launch runs only when *redo != 0
-    __amdgpu_buffer_rsrc_t rs; // over acc (built in the kernel)
-};
 
 __device__ __forceinline__ uint32_t w2_wrap(uint32_t v) { return v >= W2_RING ? v - W2_RING : v; }
 
@@ -1138,18 +1054,6 @@ k_field_bwd(FieldArgs a) {
 #define MB_ROW 20
 #define MB_WIN 64          // walk window: staged rows per chunk eighth
 #define MB_RI_CAP 4096     // merged positions of a chunk with LDS row indices (else per-row perm reads)
-#define CH_DESC 20         // chunk descriptor ints (80 B, 16-B aligned)
-#define MB_KMAX 8
-
-struct MergeArgs {
-    const int32_t* mstart;   // [B + 1] first merged position of ray r; [B] = total
-    const int32_t* perm;     // [total] merged position -> sample index
-    const int32_t* desc;     // [n_chunks][CH_DESC]: r0, r1, -, -, first sample [8], count [8]
-    int32_t* queue;          // [0] bwd ticket, [1] n_chunks, [2] fwd ticket (rn_bwd_plan)
-    float* scratch;          // [gridDim.x][rows_cap][MB_ROW]
-    float* park;             // [gridDim.x][K][BWD_WAVES][32][64]
-    int32_t n_rays, n_models, rows_cap;
-};
 
 // wave's dW accumulators <-> its park slot (lane-linear, 32 x 256 B)
 __device__ __forceinline__ void dw_park(float* p, const f32x16& A, const f32x16& B) {
@@ -1168,7 +1072,7 @@ __device__ __forceinline__ void dw_unpark(const float* p, f32x16& A, f32x16& B) 
     }
 }
 
-// GM: grid-gradient accumulation, one of GM_* (next to IntGrad).  GM_FX_REDO
+// GM: grid-gradient accumulation, one of GM_* (rn_gradform.h).  GM_FX_REDO
 // is the fp32 redo of a fixed-point or binned step that was flagged (grid
 // scatter of the levels that went in with a scale only, no dW; the launch
 // exits at once unless *F.redo is set).
@@ -1286,11 +1190,11 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
                     d[q] = reinterpret_cast<const int4*>(m.desc + (size_t)ch * CH_DESC)[q];
             }
             const int32_t* di = reinterpret_cast<const int32_t*>(d);
-            sCh[0] = ch < n_chunks ? di[0] : B; sCh[1] = ch < n_chunks ? di[1] : B;
+            sCh[0] = ch < n_chunks ? di[CH_R0] : B; sCh[1] = ch < n_chunks ? di[CH_R1] : B;
             int roff = 0;
             for (int k = 0; k < K; ++k) {
-                const int nk = ch < n_chunks ? di[4 + MB_KMAX + k] : 0;
-                sCh[2 + k] = di[4 + k]; sCh[2 + MB_KMAX + k] = nk;
+                const int nk = ch < n_chunks ? di[ch_count(k)] : 0;
+                sCh[2 + k] = di[ch_first(k)]; sCh[2 + MB_KMAX + k] = nk;
                 sCh[2 + 2 * MB_KMAX + k] = roff;
                 roff += nk;
             }
@@ -1582,947 +1486,6 @@ k_field_bwd_merged(FieldArgs a, MergeArgs m, IntGrad G, FxGrad F) {
     }
 }
 
-// ---------------------------------------------------------------------------
-// Merged forward: blocks take the plan's chunks (whole rays) and evaluate the
-// K models' tiles of a chunk interleaved (tile i of model 0, tile i of model
-// 1, ...), so the models' samples of the same rays are gathered close in time
-// by the same CU: the second model's corners hit L1/L2 lines the first one
-// fetched (the fine levels otherwise miss L2 for every sample).  With
-// K <= FM_LDS_K the K models' forward fragments sit in LDS (dynamic, K x
-// 24 KB); with more (GW), the MLP tiles read them from global memory (L2).
-// Same outputs as k_field_fwd (per-sample arithmetic is identical).
-// ---------------------------------------------------------------------------
-#define FM_KMAX 8
-#define FM_LDS_K 4
-
-template <int CACHE, bool ENC_M, bool GW>
-__global__ void __launch_bounds__(1024)
-k_field_fwd_merged(FieldArgs a, MergeArgs m) {
-    extern __shared__ __attribute__((aligned(16))) rn_half sWm[];   // [K][24 frags]
-    __shared__ LvTab sT;
-    __shared__ int32_t sCh[2][2 + 2 * FM_KMAX];      // this and the previous chunk
-    const int K = m.n_models, B = m.n_rays;
-    if (!GW) {
-        for (int k = 0; k < K; ++k)
-            rn_block_copy16(sWm + (size_t)k * FIELD_FWD_FRAGS * RN_FRAG_HALFS,
-                            a.frags + (size_t)k * FIELD_FRAGS * RN_FRAG_HALFS,
-                            FIELD_FWD_FRAGS * RN_FRAG_BYTES);
-    }
-    lv_stage(sT, a.gm);
-    const int waves = blockDim.x / RN_WAVE;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / RN_WAVE);
-    const int lane = rn_lane(), c = lane & 31, h = lane >> 5;
-    int ticket = 0, n_chunks = 0;
-    if (threadIdx.x == 0) { n_chunks = m.queue[1]; ticket = atomicAdd(m.queue + 2, 1); }
-
-    // per-model MLP tile u of chunk descriptor ch (tile i of model 0, tile i
-    // of model 1, ...); false: past the end
-    auto mlp_tile = [&](const int32_t* ch, int u) {
-        const int k = u % K, t = u / K;
-        const int n_k = ch[2 + FM_KMAX + k];
-        if (t * 32 >= n_k) return;                           // wave-uniform
-        rn_lds_order();
-        const int i = t * 32 + c;
-        const bool valid = i < n_k;
-        const int64_t s = ch[2 + k] + (valid ? i : 0);
-        FwdState st;
-        float ux, uy, uz;
-        constexpr int TC = ENC_M ? CACHE_READ_NT : CACHE;
-        const rn_half* W = GW ? a.frags + (size_t)k * FIELD_FRAGS * RN_FRAG_HALFS
-                              : sWm + (size_t)k * FIELD_FWD_FRAGS * RN_FRAG_HALFS;
-        tile_forward_s<1, TC>(a, sT, W, s, valid, TC != CACHE_NONE ? cache_slot(a, s) : nullptr,
-                              st, ux, uy, uz);
-        if (valid && h == 0) {
-            a.sigma[s] = expf(st.g0);
-            a.rgb[3 * s + 0] = sigmoidf(st.out[0]);
-            a.rgb[3 * s + 1] = sigmoidf(st.out[1]);
-            a.rgb[3 * s + 2] = sigmoidf(st.out[2]);
-        }
-    };
-    auto mlp_tiles = [&](const int32_t* ch) {
-        int max_t = 0;
-        for (int k = 0; k < K; ++k) max_t = max(max_t, (ch[2 + FM_KMAX + k] + 31) >> 5);
-        return max_t * K;
-    };
-
-    bool prev_live = false;
-    for (int it = 0;; ++it) {
-        int32_t* cur = sCh[it & 1];
-        const int32_t* prev = sCh[(it & 1) ^ 1];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int ch = ticket;
-            ticket = atomicAdd(m.queue + 2, 1);           // the next chunk's, ahead
-            int4 d[CH_DESC / 4];
-            if (ch < n_chunks) {
-#pragma unroll
-                for (int q = 0; q < CH_DESC / 4; ++q)
-                    d[q] = reinterpret_cast<const int4*>(m.desc + (size_t)ch * CH_DESC)[q];
-            }
-            const int32_t* di = reinterpret_cast<const int32_t*>(d);
-            cur[0] = ch < n_chunks ? di[0] : B;
-            cur[1] = ch < n_chunks ? di[1] : B;
-            for (int k = 0; k < K; ++k) {
-                cur[2 + k] = di[4 + k];
-                cur[2 + FM_KMAX + k] = ch < n_chunks ? di[4 + MB_KMAX + k] : 0;
-            }
-        }
-        __syncthreads();
-        const bool live = cur[0] < B;
-        if (!ENC_M) {
-            if (!live) break;
-            const int nt = mlp_tiles(cur);
-            for (int u = wid; u < nt; u += waves) mlp_tile(cur, u);
-            continue;
-        }
-        // Merged-order encoding, software-pipelined over chunks: iteration it
-        // encodes chunk it in merged (ray, t, model) order into the encoding
-        // cache -- a tile mixes the sub-NeRFs of one ray stretch, so its
-        // corners share more lines (tools/fwd_lines_sim.py: 20.9 vs 28.2 lines
-        // per sample) -- and runs the per-model MLP tiles of chunk it - 1,
-        // whose encodings the barrier above published; one work list, no
-        // barrier between the two kinds of tile.
-        if (!live && !prev_live) break;
-        int p_base = 0, n_p = 0;
-        if (live) { p_base = m.mstart[cur[0]]; n_p = m.mstart[cur[1]] - p_base; }
-        const int nA = (n_p + 31) >> 5;
-        const int nB = prev_live ? mlp_tiles(prev) : 0;
-        for (int u = wid; u < nA + nB; u += waves) {
-            if (u >= nA) { mlp_tile(prev, u - nA); continue; }
-            const int q = u * 32 + c;
-            const bool valid = q < n_p;
-            const int64_t s = m.perm[p_base + (valid ? q : 0)];
-            float x, y, z, dx, dy, dz;
-            load_sample<1>(a, s, x, y, z, dx, dy, dz);
-            const float ux = unit_coord(x, a.xyz_min[0], a.extent[0]);
-            const float uy = unit_coord(y, a.xyz_min[1], a.extent[1]);
-            const float uz = unit_coord(z, a.xyz_min[2], a.extent[2]);
-            half8 e0, e1;
-            encode_lane(a, sT, rn_rsrc(a.grid, a.grid_bytes), h, ux, uy, uz, valid, e0, e1);
-            if (valid) { half8* fc = cache_slot(a, s); fc[0] = e0; fc[1] = e1; }
-        }
-        prev_live = live;
-    }
-}
-
-
-// ---------------------------------------------------------------------------
-// Level-partitioned forward (round 3, after a probe: tools/enc_probe.py).
-// The merged forward gathers all sixteen levels of a sample on one CU, so
-// every XCD's 4 MB L2 faces the whole 23 MB table and the fine levels miss
-// it for nearly every sample (27 fabric requests per sample at C5).  Here
-// the encoding is split by level instead:
-//   1. k_enc_prep: per merged position p the sample's unit coordinates and
-//      index (16 B), computed once (bit-identical to load_sample<1>);
-//   2. k_field_encode_levels: block b encodes levels g and 15 - g, g = b % 8,
-//      for every sample (one level after the other).  Workgroups are dispatched to the XCDs round-robin
-//      (a rotation that varies by dispatch: measured, group g ran on XCD
-//      g - 1 for all its blocks), so each XCD gathers from two levels' tables
-//      only; correctness does not depend on the mapping.  Output: one f16x2
-//      plane per level, planes[L][s] (bit-identical to encode_lane);
-//   3. k_field_mlp_planes: the MLP tiles per model read the 8 levels of each
-//      lane from the planes, write sigma / rgb and the encoding cache (tile
-//      layout) that the backward and the input-gradient kernels read.
-// Static splits, no ticket queues (a per-XCD ticket word serialised at
-// ~100 ns per ticket: 1.9 ms at C3).
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_enc_prep(FieldArgs a, MergeArgs m, float4* __restrict__ prep) {
-    const int P = m.mstart[m.n_rays];
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        const int s = m.perm[p];
-        float x, y, z, dx, dy, dz;
-        load_sample<1>(a, s, x, y, z, dx, dy, dz);
-        prep[p] = make_float4(unit_coord(x, a.xyz_min[0], a.extent[0]),
-                              unit_coord(y, a.xyz_min[1], a.extent[1]),
-                              unit_coord(z, a.xyz_min[2], a.extent[2]), __int_as_float(s));
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_field_encode_levels(FieldArgs a, MergeArgs m, const float4* __restrict__ prep,
-                      int32_t* __restrict__ xq, uint64_t pairing) {
-    __shared__ LvTab sT;
-    lv_stage(sT, a.gm);
-    __syncthreads();
-    const int g = blockIdx.x & 7;
-    if (xq && threadIdx.x == 0) {           // probe: group g's blocks per XCD, its span
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-        atomicAdd(xq + 8 * g + (int)(xcc & 7u), 1);
-        atomicMin(reinterpret_cast<unsigned long long*>(xq + 64) + g,
-                  (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    }
-    // group g's levels: byte g of `pairing` (low nibble la, high lb)
-    const int la = (int)((pairing >> (8 * g)) & 15u), lb = (int)((pairing >> (8 * g + 4)) & 15u);
-    const int P = m.mstart[m.n_rays];
-    const int nt = (P + 31) >> 5;
-    const int nb = (int)(gridDim.x >> 3), j = (int)(blockIdx.x >> 3);
-    const int t0 = (int)((int64_t)nt * j / nb), t1 = (int)((int64_t)nt * (j + 1) / nb);
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
-    const int lane = rn_lane(), c = lane & 31, h = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs = rn_rsrc(a.grid, a.grid_bytes);
-    const LvConst LA = lv_const_uniform(sT, a.gm, la), LB = lv_const_uniform(sT, a.gm, lb);
-    // level la over the block's tiles, then level lb: the XCD's blocks run in
-    // step, so its L2 holds one level's table at a time (two hashed levels at
-    // once, 4 MB, filled the whole L2).  A wave takes two tiles per pass.
-#pragma unroll 1
-    for (int ph = 0; ph < 2; ++ph) {
-        const LvConst& LC = ph ? LB : LA;
-        uint32_t* const out = const_cast<uint32_t*>(a.planes) + (size_t)(ph ? lb : la) * a.plane_stride;
-        for (int t = t0 + 2 * wid; t < t1; t += 2 * waves) {
-            const bool v0 = t * 32 + c < P;
-            const bool v1 = t + 1 < t1 && (t + 1) * 32 + c < P;
-            const bool valid = h ? v1 : v0;
-            const int p = (t + h) * 32 + c;
-            const float4 q = prep[valid ? p : 0];
-            const uint32_t v = encode_tiles(a, rs, h, LC, q.x, q.y, q.z, v0, v1);
-            if (valid) __builtin_nontemporal_store(v, out + __float_as_int(q.w));
-        }
-    }
-    if (xq) {
-        __syncthreads();
-        if (threadIdx.x == 0)
-            atomicMax(reinterpret_cast<unsigned long long*>(xq + 80) + g,
-                      (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    }
-}
-
-// MLP tiles of the K models (tile u of the flat list: model k's 32 samples
-// from seg_base[k] + 32 t).  Block b takes a contiguous range of the list,
-// which spans one or two models at the bench sizes; their forward fragments
-// are staged in LDS, FM_LDS_K models at a time.
-__global__ void __launch_bounds__(1024)
-k_field_mlp_planes(FieldArgs a, int K) {
-    extern __shared__ __attribute__((aligned(16))) rn_half sWm[];   // [<= FM_LDS_K][24 frags]
-    __shared__ LvTab sT;
-    // the K segments (first sample, count), read once: per tile they were a
-    // global round trip ahead of the tile's dependent loads
-    __shared__ int32_t sSeg[2][FM_KMAX];
-    lv_stage(sT, a.gm);
-    if (threadIdx.x < K) {
-        sSeg[0][threadIdx.x] = a.seg_base[threadIdx.x];
-        sSeg[1][threadIdx.x] = a.seg_count[threadIdx.x];
-    }
-    int first[FM_KMAX + 1];
-    first[0] = 0;
-    for (int k = 0; k < K; ++k)
-        first[k + 1] = first[k] + ((__builtin_amdgcn_readfirstlane(a.seg_count[k]) + 31) >> 5);
-    const int T = first[K];
-    const int u0 = (int)((int64_t)T * blockIdx.x / gridDim.x);
-    const int u1 = (int)((int64_t)T * (blockIdx.x + 1) / gridDim.x);
-    if (u0 >= u1) return;                                   // block-uniform
-    int k_lo = 0, k_hi = 0;
-    for (int k = 0; k < K; ++k) {
-        if (first[k + 1] <= u0) k_lo = k + 1;
-        if (first[k] < u1) k_hi = k;
-    }
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
-    const int lane = rn_lane(), c = lane & 31, h = lane >> 5;
-    for (int kb = k_lo; kb <= k_hi; kb += FM_LDS_K) {
-        const int ke = min(k_hi, kb + FM_LDS_K - 1);
-        __syncthreads();                                    // previous models' tiles done
-        for (int k = kb; k <= ke; ++k)
-            rn_block_copy16(sWm + (size_t)(k - kb) * FIELD_FWD_FRAGS * RN_FRAG_HALFS,
-                            a.frags + (size_t)k * FIELD_FRAGS * RN_FRAG_HALFS,
-                            FIELD_FWD_FRAGS * RN_FRAG_BYTES);
-        __syncthreads();
-        const int ua = max(u0, first[kb]), ub = min(u1, first[ke + 1]);
-        for (int u = ua + wid; u < ub; u += waves) {
-            int k = kb;
-            while (k < ke && u >= first[k + 1]) ++k;
-            const int t = u - first[k];
-            const int n_k = sSeg[1][k];
-            const int i = t * 32 + c;
-            const bool valid = i < n_k;
-            const int64_t s = sSeg[0][k] + (valid ? i : 0);
-            FwdState st;
-            float ux, uy, uz;
-            rn_lds_order();
-            tile_forward_s<1, CACHE_PLANES>(a, sT, sWm + (size_t)(k - kb) * FIELD_FWD_FRAGS * RN_FRAG_HALFS,
-                                            s, valid, a.feat ? cache_slot(a, s) : nullptr, st,
-                                            ux, uy, uz);
-            if (valid && h == 0) {
-                a.sigma[s] = expf(st.g0);
-                a.rgb[3 * s + 0] = sigmoidf(st.out[0]);
-                a.rgb[3 * s + 1] = sigmoidf(st.out[1]);
-                a.rgb[3 * s + 2] = sigmoidf(st.out[2]);
-            }
-        }
-    }
-}
-
-
-// Integer-mode scale: 2^(26 - e) with 2^(e-1) <= M < 2^e, M the largest
-// backward seed of the step (|dL/dsigma * sigma|, |dL/drgb|), so a seed-sized
-// contribution is ~2^26 units; larger ones carry exactly.
-__global__ void __launch_bounds__(256)
-k_seed_max(const int32_t* __restrict__ seg_base, const int32_t* __restrict__ seg_count,
-           const float* __restrict__ sigma, const float* __restrict__ dsigma,
-           const float* __restrict__ drgb, uint32_t* __restrict__ mbits) {
-    const int k = blockIdx.y;
-    const int64_t base = seg_base[k], n = seg_count[k];
-    float mx = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = base + i;
-        mx = fmaxf(mx, fabsf(dsigma[s] * sigma[s]));
-        mx = fmaxf(mx, fmaxf(fabsf(drgb[3 * s]), fmaxf(fabsf(drgb[3 * s + 1]), fabsf(drgb[3 * s + 2]))));
-    }
-    mx = rn_wave_max(mx);
-    if (rn_lane() == 0 && mx > 0.f && isfinite(mx)) atomicMax(mbits, __float_as_uint(mx));
-}
-
-__global__ void k_seed_scale(const uint32_t* __restrict__ mbits, float* __restrict__ scale) {
-    const float m = __uint_as_float(*mbits);
-    float sc = 1.0f;
-    if (m > 0.f) {
-        int e;
-        frexpf(m, &e);                   // m = f * 2^e, f in [0.5, 1)
-        sc = scalbnf(1.0f, max(-100, min(100, 26 - e)));
-    }
-    *scale = sc;
-}
-
-// grid_grad += (carry * 2^32 + lo) / scale; lo = carry = 0 for the next step
-__global__ void __launch_bounds__(256)
-k_igrad_to_f32(int64_t n, int32_t* __restrict__ lo, int32_t* __restrict__ carry,
-               const float* __restrict__ scale, float* __restrict__ grad) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double v = ((double)carry[i] * 4294967296.0 + (double)lo[i]) / (double)*scale;
-    grad[i] += (float)v;
-    lo[i] = 0;
-    carry[i] = 0;
-}
-
-// Exact per-level sum of the int32 entries (int64), for the net-wrap check,
-// and the level's largest |entry| in gradient units (the next step's scale
-// keeps it in range): from the int32 entries of a fixed-point level, from
-// grid_grad for a level that went in as fp32 this step (the first step; an
-// upper bound when the caller accumulates several steps into grid_grad).
-__global__ void __launch_bounds__(256)
-k_fx_esum(GridMeta gm, const float* __restrict__ scale, const int32_t* __restrict__ acc,
-          const float* __restrict__ grad, FxStats* __restrict__ st) {
-    const int l = blockIdx.y;
-    const float sc = scale[l];
-    typedef int vi4 __attribute__((ext_vector_type(4)));
-    const int64_t e0 = 2 * (int64_t)gm.offset[l], n4 = (2 * (int64_t)gm.hsize[l]) >> 2;
-    int64_t s = 0;
-    uint64_t ws = 0;                 // sum of entry * fx_weight(element), mod 2^64
-    uint32_t mx = 0u;           // fixed point: |int|; fp32 level: |float| bits
-    auto uabs = [](int x) { return x < 0 ? 0u - (uint32_t)x : (uint32_t)x; };
-    if (sc != 0.f) {
-        const vi4* a4 = reinterpret_cast<const vi4*>(acc + e0);
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-             i += (int64_t)gridDim.x * blockDim.x) {
-            const vi4 v = __builtin_nontemporal_load(a4 + i);
-            s += (int64_t)v.x + v.y + v.z + v.w;
-            const uint32_t el = (uint32_t)(e0 + 4 * i);
-            ws += (uint64_t)((int64_t)v.x * (int64_t)fx_weight(el)) +
-                  (uint64_t)((int64_t)v.y * (int64_t)fx_weight(el + 1)) +
-                  (uint64_t)((int64_t)v.z * (int64_t)fx_weight(el + 2)) +
-                  (uint64_t)((int64_t)v.w * (int64_t)fx_weight(el + 3));
-            mx = max(max(mx, max(uabs(v.x), uabs(v.y))), max(uabs(v.z), uabs(v.w)));
-        }
-    } else {
-        const vi4* g4 = reinterpret_cast<const vi4*>(grad + e0);
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-             i += (int64_t)gridDim.x * blockDim.x) {
-            const vi4 v = __builtin_nontemporal_load(g4 + i);
-            mx = max(max(mx, max((uint32_t)v.x & 0x7fffffffu, (uint32_t)v.y & 0x7fffffffu)),
-                     max((uint32_t)v.z & 0x7fffffffu, (uint32_t)v.w & 0x7fffffffu));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s += __shfl_xor(s, off);
-        ws += __shfl_xor(ws, off);
-        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
-    }
-    // one atomic per block (per-wave atomics on the level words serialised:
-    // 107 us for 16k of them)
-    __shared__ int64_t sW[4];
-    __shared__ uint64_t sWw[4];
-    __shared__ uint32_t sM[4];
-    const int w = threadIdx.x / RN_WAVE;
-    if (rn_lane() == 0) { sW[w] = s; sWw[w] = ws; sM[w] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int64_t t = (sW[0] + sW[1]) + (sW[2] + sW[3]);
-        const uint64_t tw = (sWw[0] + sWw[1]) + (sWw[2] + sWw[3]);
-        if (tw != 0) atomicAdd(reinterpret_cast<unsigned long long*>(st->we + l), tw);
-        uint32_t m = max(max(sM[0], sM[1]), max(sM[2], sM[3]));
-        if (sc != 0.f) m = __float_as_uint((float)m / sc);     // units -> gradient units
-        if (t != 0) atomicAdd(reinterpret_cast<unsigned long long*>(st->esum + l), (unsigned long long)t);
-        if (m != 0u && m < 0x7f800000u) atomicMax(st->emax + l, m);
-    }
-}
-
-// Fixed-point step bookkeeping (one wave): redo flag of this step, the next
-// step's per-level scales from this step's largest records, statistics reset.
-// Scale 2^(FX_TARGET_BITS - e) with |record| < 2^e: the largest record maps
-// to < 2^27 units.  A level whose largest record reached 2^30 units under the
-// current scale (8x growth since the step the scale came from), or a
-// non-finite one, or whose entries wrapped (entry sum != record sum), sets the
-// redo flag: rn_grid_fx_fold then discards the fixed-point sums and the GM_FX_REDO
-// launch recomputes the grid gradient in fp32.
-// Headroom measured on C3 over 12 Adam steps (tools/fx_diag.py): the largest
-// |entry| of a hashed level stays within 2^1.2 of its largest record, so at
-// 2^27 units it sits ~2^3 below the int32 range.  A dense (coarse) level's
-// entry sums up to hundreds of records, so its scale is also capped by this
-// step's largest |entry|: it maps to < 2^29 units (2^2 of headroom for growth;
-// the first step's entries are read from the fp32 grid_grad); a dense level
-// with no entry measured maps its largest record to < 2^14 units.
-// Why these units (round 6; tools/fx_units_probe.py,
-// profiles/r06/fxunits/): FusedAdam's eps 1e-15 turns any non-zero gradient
-// into an lr-sized step, so an entry below half a unit (flushed to 0) moves
-// the update as much as a wrong sign.  C3, 3 Adam steps, largest per-level
-// update difference from fp32 (fp32 with the rays reversed: <= 0.07 %):
-// 2048 rays 2.66 % at (23, 28, 28) -> 1.14 % at (27, 29, 30); 8192 rays 1.02
-// -> 0.38 %; flushed entries 0.031 -> 0.005 %; no step redone in 1,150
-// probe and training steps; 1000 training steps end within 0.03 dB of fp32
-// either way.  (26, 30, 30) redid one of 1000 training steps (entry cap too
-// close to 2^31).
-#ifndef FX_TARGET_BITS              // (-D overrides: unit studies, tools/fx_units_probe.py)
-#define FX_TARGET_BITS 27
-#endif
-#ifndef FX_ENTRY_BITS
-#define FX_ENTRY_BITS 29
-#endif
-#define FX_DENSE_FIRST_BITS 14
-#ifndef FX_GROWTH_BITS
-#define FX_GROWTH_BITS 30
-#endif
-#define FX_GROWTH_UNITS ((float)(1u << FX_GROWTH_BITS))   // 2^30
-// Binned mode (ctl != NULL, rn_grid_binned_fold): records are e5m17 (rn_bin.h),
-// summed exactly in int64, so there is no entry cap and no wrap check; the
-// largest record maps to < 2^GB_TARGET_BITS = 2^38 units (256x headroom below
-// 2^46, the first value e5m17 cannot hold: a record that reaches it sets the
-// redo flag -- the bar is exact, every record below it is representable), and
-// so does a pool overflow (the walk ran out of pages) or a fault word the bin
-// pass set (inputs out of range).
-__global__ void __launch_bounds__(64)
-k_fx_check(uint32_t hashed_mask, const float* __restrict__ scale_cur,
-           float* __restrict__ scale_next, FxStats* __restrict__ stats,
-           int32_t* __restrict__ redo, const GbCtl* __restrict__ ctl, uint32_t pool_pages) {
-    const int l = threadIdx.x;
-    uint32_t* vmax = stats->vmax;
-    const bool binned = ctl != nullptr;
-    // pool overflow, or inputs the bin pass refused (GbCtl::fault)
-    bool bad = binned && l == 0 && (ctl->pool_next > pool_pages || ctl->fault != 0u);
-    const float growth = binned ? GB_GROWTH_UNITS : FX_GROWTH_UNITS;
-    if (l < RN_L) {
-        // net wrap of an int32 entry: the entries' exact sum differs from the
-        // records' exact sum (by a multiple of 2^32)
-        // (and the position-weighted sums: opposite wraps cancel only in the plain one)
-        if (!binned && scale_cur[l] != 0.f &&
-            (stats->esum[l] != stats->qsum[l] || stats->we[l] != stats->wq[l]))
-            bad = true;
-        stats->esum[l] = 0;
-        stats->qsum[l] = 0;
-        stats->we[l] = 0;
-        stats->wq[l] = 0;
-        const uint32_t vb = vmax[l];
-        const float sc = scale_cur[l];
-        const uint32_t em = stats->emax[l];
-        float nx = sc;                                   // no records this step: keep
-        if (vb >= 0x7f800000u) {                         // inf / NaN record
-            nx = 0.f;
-            bad = bad || sc != 0.f;
-        } else if (vb != 0u) {
-            const float v = __uint_as_float(vb);
-            bad = bad || (sc != 0.f && v * sc >= growth);
-            int e;
-            frexpf(v, &e);                               // v < 2^e
-            int bits = (binned ? GB_TARGET_BITS : FX_TARGET_BITS) - e;
-            if (binned) {
-                // int64 sums: no entry cap
-            } else if (em != 0u) {                       // the largest entry stays < 2^29 units
-                int ee;
-                frexpf(__uint_as_float(em), &ee);
-                bits = min(bits, FX_ENTRY_BITS - ee);
-            } else if (!((hashed_mask >> l) & 1u)) {     // dense level, no entry measured
-                bits = FX_DENSE_FIRST_BITS - e;
-            }
-            nx = scalbnf(1.0f, max(-126, min(126, bits)));
-        }
-        scale_next[l] = nx;
-        vmax[l] = 0u;
-        stats->emax[l] = 0u;
-    }
-    const uint64_t b = __builtin_amdgcn_ballot_w64(bad);
-    if (l == 0) *redo = b ? 1 : 0;
-}
-
-// grid_grad += acc * 2^-e_l over the fixed-point levels' entries (elements
-// [e0, e1), 16-B aligned), acc = 0; with the redo flag set the sums are only
-// cleared (the fp32 redo adds the step's gradient instead).
-__global__ void __launch_bounds__(256)
-k_fx_fold(int64_t e0, int64_t e1, GridMeta gm, const float* __restrict__ scale,
-          int32_t* __restrict__ acc, float* __restrict__ grad, const int32_t* __restrict__ redo) {
-    __shared__ uint32_t sOff[RN_L];
-    __shared__ float sInv[RN_L];
-    if (threadIdx.x < RN_L) {
-        sOff[threadIdx.x] = gm.offset[threadIdx.x];
-        const float sc = scale[threadIdx.x];
-        sInv[threadIdx.x] = sc != 0.f ? 1.0f / sc : 0.f;     // exact: powers of two
-    }
-    __syncthreads();
-    const bool discard = *redo != 0;
-    const int64_t n4 = (e1 - e0) >> 2;
-    typedef int vi4 __attribute__((ext_vector_type(4)));
-    vi4* a4 = reinterpret_cast<vi4*>(acc + e0);
-    float4* g4 = reinterpret_cast<float4*>(grad + e0);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const vi4 v = __builtin_nontemporal_load(a4 + i);
-        if ((v.x | v.y | v.z | v.w) == 0) continue;
-        __builtin_nontemporal_store(vi4{0, 0, 0, 0}, a4 + i);
-        if (discard) continue;
-        const uint32_t ent = (uint32_t)((e0 + 4 * i) >> 1);
-        int l = 0;
-#pragma unroll
-        for (int k = 1; k < RN_L; ++k) l = ent >= sOff[k] ? k : l;
-        const float inv = sInv[l];
-        float4 g = g4[i];
-        g.x += (float)v.x * inv; g.y += (float)v.y * inv;
-        g.z += (float)v.z * inv; g.w += (float)v.w * inv;
-        g4[i] = g;
-    }
-}
-
-// Merged order of the K models' samples per ray (ray-major, then t, ties by
-// model): perm[mstart[r] + rank] = sample.  One wave per ray; each sample's
-// rank = its index in its (model, ray) run + the samples of the other models
-// of the ray that precede it (binary search; t increases along a run).  The
-// ray's K runs are staged in the wave's LDS slice when they fit (always for
-// K = 2), so the searches are LDS reads instead of dependent global loads.
-#define PLAN_WAVES 4
-#define PLAN_LDS 2048      // floats per wave
-
-// Stage one ray's K runs of t (and, with ids, each sample's position in the
-// concatenation) into the wave's LDS slice: position i of the concatenated
-// runs [bnd[k], bnd[k+1]) is sample off[k] + i - bnd[k].  Positions are dealt
-// over the lanes with PLAN_UNR loads in flight per lane (a loop per run, one
-// load then its store, waited for each load: 16 round trips per ray at K = 8,
-// and k_bwd_plan_multi took 0.139 ms at C5).  bnd / off are wave-uniform.
-#define PLAN_UNR 8
-
-// The level-partitioned forward's per-position input (k_enc_prep's float4:
-// unit coordinates, sample id), written by the plan as it places each sample
-// (rn_bwd_plan with `prep`): the plan has the sample's t in LDS and its ray,
-// so the separate pass that re-read perm, ts and the ray (C3 0.03 ms) goes.
-// Arithmetic as load_sample<1> + unit_coord (bit-identical).
-struct PlanPrep {
-    float4* prep;             // null: the plan writes perm only
-    const float* rays_o; const float* rays_d;
-    float mn[3], ext[3];
-    // 1 / extent when every extent is a power of two (scale 0.5: 1, scale 16:
-    // 32): x / ext and x * (1 / ext) are then the same float, and the three
-    // IEEE divisions per sample leave the merge's serial chain; 0 otherwise
-    float inv[3];
-};
-struct RayPos { float o[3], d[3]; };
-__device__ __forceinline__ RayPos plan_ray(const PlanPrep& P, int r) {
-    RayPos q;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { q.o[c] = P.rays_o[3 * r + c]; q.d[c] = P.rays_d[3 * r + c]; }
-    return q;
-}
-__device__ __forceinline__ void plan_prep_write(const PlanPrep& P, const RayPos& q, int pos,
-                                                float t, int s) {
-    const float x = fmaf(t, q.d[0], q.o[0]), y = fmaf(t, q.d[1], q.o[1]), z = fmaf(t, q.d[2], q.o[2]);
-    auto u = [&](float v, int c) {
-        return P.inv[0] != 0.f ? fminf(fmaxf((v - P.mn[c]) * P.inv[c], 0.0f), 1.0f)
-                               : unit_coord(v, P.mn[c], P.ext[c]);
-    };
-    P.prep[pos] = make_float4(u(x, 0), u(y, 1), u(z, 2), __int_as_float(s));
-}
-
-// Ray r's run of each model (count, first sample) and its merged start ms.
-// r is wave-uniform (the wave id read back as a scalar), and every model's
-// words load unconditionally (index clamped to K - 1, zeroed after): scalar
-// loads issued together.  (With the wave id a vector value and each load
-// under k < K, the 2K counts / offsets became vector loads waited for one by
-// one: ~16 round trips per ray at K = 8.)
-__device__ __forceinline__ void plan_ray_runs(int K, int B, int r, const int32_t* __restrict__ counts,
-                                              const int32_t* __restrict__ offsets,
-                                              const int32_t* __restrict__ seg_base, int* cnt,
-                                              int* off, int& ms) {
-    int c[MB_KMAX], o[MB_KMAX], sb[MB_KMAX];
-#pragma unroll
-    for (int k = 0; k < MB_KMAX; ++k) {
-        const int kk = k < K ? k : K - 1;
-        c[k] = counts[kk * B + r]; o[k] = offsets[kk * B + r]; sb[k] = seg_base[kk];
-    }
-    ms = 0;
-#pragma unroll
-    for (int k = 0; k < MB_KMAX; ++k) {
-        cnt[k] = k < K ? c[k] : 0;
-        off[k] = k < K ? o[k] : 0;
-        ms += k < K ? o[k] - sb[k] : 0;
-    }
-}
-__device__ __forceinline__ void plan_stage(int K, int tot_r, const int* bnd, const int* off,
-                                           const float* __restrict__ ts, float* st, uint16_t* si) {
-    const int lane = rn_lane();
-    for (int i0 = 0; i0 < tot_r; i0 += RN_WAVE * PLAN_UNR) {
-        float v[PLAN_UNR];
-#pragma unroll
-        for (int u = 0; u < PLAN_UNR; ++u) {
-            const int i = i0 + u * RN_WAVE + lane;
-            int base = off[0];                    // off[k] - bnd[k] of i's run (bnd[0] = 0)
-#pragma unroll
-            for (int kq = 1; kq < MB_KMAX; ++kq)
-                base = (kq < K && i >= bnd[kq]) ? off[kq] - bnd[kq] : base;
-            v[u] = i < tot_r ? ts[base + i] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < PLAN_UNR; ++u) {
-            const int i = i0 + u * RN_WAVE + lane;
-            if (i < tot_r) {
-                st[i] = v[u];
-                if (si) si[i] = (uint16_t)i;
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(PLAN_WAVES * 64)
-k_bwd_plan(int B, int K, const int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
-           const int32_t* __restrict__ seg_base, const int32_t* __restrict__ seg_count,
-           const float* __restrict__ ts, int32_t* __restrict__ mstart, int32_t* __restrict__ perm,
-           PlanPrep P) {
-    __shared__ float sT[PLAN_WAVES][PLAN_LDS];
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / RN_WAVE);
-    const int r = blockIdx.x * PLAN_WAVES + wid;
-    if (r >= B) return;                      // wave-uniform; no block barrier below
-    const int lane = rn_lane();
-    int ms = 0, tot_r = 0;
-    int cnt[MB_KMAX], off[MB_KMAX], loc[MB_KMAX];
-    plan_ray_runs(K, B, r, counts, offsets, seg_base, cnt, off, ms);
-#pragma unroll
-    for (int k = 0; k < MB_KMAX; ++k) { loc[k] = tot_r; tot_r += cnt[k]; }
-    if (lane == 0) {
-        mstart[r] = ms;
-        if (r == 0) {
-            int tot = 0;
-            for (int k = 0; k < K; ++k) tot += seg_count[k];
-            mstart[B] = tot;
-        }
-    }
-    const bool staged = tot_r <= PLAN_LDS;
-    float* st = sT[wid];
-    const RayPos rq = P.prep ? plan_ray(P, r) : RayPos{};
-    if (staged) {
-        plan_stage(K, tot_r, loc, off, ts, st, nullptr);
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    }
-    if (K == 2 && staged) {
-        // merge path: lane j emits merged positions [j L, (j+1) L); it finds
-        // how many of them come from model 0 by a binary search on its
-        // diagonal (model 0 first on equal t, as below), then merges serially
-        // -- ~log2(n) + L dependent LDS reads per lane instead of a search
-        // per sample (C3: 0.064 -> 0.040 ms with k_bwd_chunks)
-        const float* A = st + loc[0];
-        const float* Bv = st + loc[1];
-        const int nA = cnt[0], nB = cnt[1], n = nA + nB;
-        const int L = (n + RN_WAVE - 1) / RN_WAVE;
-        const int d = min(lane * L, n);
-        int lo = max(0, d - nB), hi = min(d, nA);
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (A[mid] <= Bv[d - 1 - mid]) lo = mid + 1; else hi = mid;
-        }
-        int a = lo, b = d - lo;
-        const int e = min(d + L, n);
-        for (int q = d; q < e; ++q) {
-            const bool takeA = a < nA && (b >= nB || A[a] <= Bv[b]);
-            const int smp = takeA ? off[0] + a : off[1] + b;
-            perm[ms + q] = smp;
-            if (P.prep) plan_prep_write(P, rq, ms + q, takeA ? A[a] : Bv[b], smp);
-            a += takeA ? 1 : 0;
-            b += takeA ? 0 : 1;
-        }
-        return;
-    }
-    for (int k = 0; k < K; ++k) {
-        for (int i = lane; i < cnt[k]; i += RN_WAVE) {
-            const float t = staged ? st[loc[k] + i] : ts[off[k] + i];
-            int pos = i;
-            for (int k2 = 0; k2 < K; ++k2) {
-                if (k2 == k) continue;
-                int lo = 0, hi = cnt[k2];        // count of t2 < t (k2 > k) or t2 <= t (k2 < k)
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    const float t2 = staged ? st[loc[k2] + mid] : ts[off[k2] + mid];
-                    if (t2 < t || (k2 < k && t2 == t)) lo = mid + 1; else hi = mid;
-                }
-                pos += lo;
-            }
-            perm[ms + pos] = off[k] + i;
-            if (P.prep) plan_prep_write(P, rq, ms + pos, t, off[k] + i);
-        }
-    }
-}
-
-// The same merged order for K > 2 by a merge tree in LDS: the ray's K runs
-// (staged with their sample indices) are merged pairwise, log2(K) levels; each
-// pair is merged by the whole wave with merge path (lane j: a diagonal binary
-// search, then L serial steps).  Runs are merged in model order and the left
-// run wins ties, so the result is ordered by (t, model) like k_bwd_plan's
-// ranks.  ~log2(n) + n/64 dependent LDS reads per lane and level instead of
-// (K-1) binary searches per sample (C5: K = 8, ~760 samples per ray).
-#define PLANM_WAVES 2
-#define PLANM_LDS 2048     // samples per wave
-
-// Sample ids in LDS are u16 positions in the ray's staged runs (model k's run
-// starts at kb[k]); the last level maps them to global sample indices
-// (ko[k] + id - kb[k]).  u16 ids take a block to 48 KB of LDS: 3 blocks (6
-// waves) per CU instead of 2, for a latency-bound merge.
-__device__ __forceinline__ void merge_pair_wave(const float* tA, const uint16_t* iA, int nA,
-                                                const float* tB, const uint16_t* iB, int nB,
-                                                float* to, uint16_t* io, int32_t* gout,
-                                                const int* kb, const int* ko, int K,
-                                                const PlanPrep& P, const RayPos& rq, int gpos) {
-    const int lane = rn_lane();
-    const int n = nA + nB;
-    const int L = (n + RN_WAVE - 1) / RN_WAVE;
-    const int d = min(lane * L, n);
-    int lo = max(0, d - nB), hi = min(d, nA);
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (tA[mid] <= tB[d - 1 - mid]) lo = mid + 1; else hi = mid;
-    }
-    int a = lo, b = d - lo;
-    const int e = min(d + L, n);
-    for (int q = d; q < e; ++q) {
-        // both heads' t and ids read together (one LDS round trip per step;
-        // as selects of the addresses, the compare, the id and the output t
-        // were three).  a = nA / b = nB read one past their run, inside the
-        // wave's slice, and are not used
-        const float ta = tA[a], tb = tB[b];
-        const int ja = iA[a], jb = iB[b];
-        const bool takeA = a < nA && (b >= nB || ta <= tb);
-        const int idx = takeA ? ja : jb;
-        if (gout) {
-            int base = ko[0];
-#pragma unroll
-            for (int j = 1; j < MB_KMAX; ++j)
-                if (j < K && idx >= kb[j]) base = ko[j] - kb[j];
-            gout[q] = base + idx;
-            if (P.prep) plan_prep_write(P, rq, gpos + q, takeA ? ta : tb, base + idx);
-        } else {
-            to[q] = takeA ? ta : tb;
-            io[q] = (uint16_t)idx;
-        }
-        a += takeA ? 1 : 0;
-        b += takeA ? 0 : 1;
-    }
-}
-
-__global__ void __launch_bounds__(PLANM_WAVES * 64)
-k_bwd_plan_multi(int B, int K, const int32_t* __restrict__ counts,
-                 const int32_t* __restrict__ offsets, const int32_t* __restrict__ seg_base,
-                 const int32_t* __restrict__ seg_count, const float* __restrict__ ts,
-                 int32_t* __restrict__ mstart, int32_t* __restrict__ perm, PlanPrep P) {
-    // (+2: a merge step reads one past the last run)
-    __shared__ float sT[PLANM_WAVES][2][PLANM_LDS + 2];
-    __shared__ uint16_t sI[PLANM_WAVES][2][PLANM_LDS + 2];
-    static_assert(PLANM_LDS <= 65536, "u16 sample ids");
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / RN_WAVE);
-    const int r = blockIdx.x * PLANM_WAVES + wid;
-    if (r >= B) return;                      // wave-uniform; no block barrier below
-    const int lane = rn_lane();
-    int ms = 0, tot_r = 0;
-    int bnd[MB_KMAX + 1], off[MB_KMAX], cnt[MB_KMAX];
-    plan_ray_runs(K, B, r, counts, offsets, seg_base, cnt, off, ms);
-#pragma unroll
-    for (int k = 0; k < MB_KMAX; ++k) { bnd[k] = tot_r; tot_r += cnt[k]; }
-    bnd[MB_KMAX] = tot_r;
-    const RayPos rq = P.prep ? plan_ray(P, r) : RayPos{};
-    if (lane == 0) {
-        mstart[r] = ms;
-        if (r == 0) {
-            int tot = 0;
-            for (int k = 0; k < K; ++k) tot += seg_count[k];
-            mstart[B] = tot;
-        }
-    }
-    if (tot_r > PLANM_LDS) {
-        // (rays longer than the LDS slice: rank by binary searches in global memory)
-        for (int k = 0; k < K; ++k) {
-            const int ck = bnd[k + 1] - bnd[k];
-            for (int i = lane; i < ck; i += RN_WAVE) {
-                const float t = ts[off[k] + i];
-                int pos = i;
-                for (int k2 = 0; k2 < K; ++k2) {
-                    if (k2 == k) continue;
-                    int lo = 0, hi = bnd[k2 + 1] - bnd[k2];
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        const float t2 = ts[off[k2] + mid];
-                        if (t2 < t || (k2 < k && t2 == t)) lo = mid + 1; else hi = mid;
-                    }
-                    pos += lo;
-                }
-                perm[ms + pos] = off[k] + i;
-                if (P.prep) plan_prep_write(P, rq, ms + pos, t, off[k] + i);
-            }
-        }
-        return;
-    }
-    int cur = 0;
-    int kb[MB_KMAX];                          // the models' runs (bnd is merged below)
-#pragma unroll
-    for (int k = 0; k < MB_KMAX; ++k) kb[k] = k < K ? bnd[k] : 0;
-    plan_stage(K, tot_r, bnd, off, ts, sT[wid][0], sI[wid][0]);
-    int nr = K;
-    while (true) {
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const bool last = nr <= 2;
-        const float* ts_ = sT[wid][cur];
-        const uint16_t* is_ = sI[wid][cur];
-        for (int p = 0; 2 * p < nr; ++p) {
-            const int a0 = bnd[2 * p], a1 = bnd[min(2 * p + 1, nr)], b1 = bnd[min(2 * p + 2, nr)];
-            merge_pair_wave(ts_ + a0, is_ + a0, a1 - a0, ts_ + a1, is_ + a1, b1 - a1,
-                            sT[wid][cur ^ 1] + a0, sI[wid][cur ^ 1] + a0,
-                            nullptr, kb, off, K, P, rq, ms + a0);
-        }
-        if (last) {
-            // the merged order is in LDS like every level's: perm (and the
-            // level forward's input) go out in position order, coalesced and
-            // off the merge's serial chain (written from inside it, each
-            // lane's stores were L positions apart)
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const float* to = sT[wid][cur ^ 1];
-            const uint16_t* io = sI[wid][cur ^ 1];
-            for (int q = lane; q < tot_r; q += RN_WAVE) {
-                const int idx = io[q];
-                int base = off[0];
-#pragma unroll
-                for (int jk = 1; jk < MB_KMAX; ++jk)
-                    if (jk < K && idx >= kb[jk]) base = off[jk] - kb[jk];
-                perm[ms + q] = base + idx;
-                if (P.prep) plan_prep_write(P, rq, ms + q, to[q], base + idx);
-            }
-            return;
-        }
-        // runs after this level: boundaries of the merged pairs
-        const int nn = (nr + 1) / 2;
-        for (int p = 0; p < nn; ++p) bnd[p] = bnd[2 * p];
-        bnd[nn] = bnd[nr];
-        nr = nn;
-        cur ^= 1;
-    }
-}
-
-// Chunk schedule of the merged backward over the merged positions [0, total):
-// big chunks for the first 15/16 of the work, then chunks of min_chunk (a short
-// tail: blocks finish together).  With `blocks` > 0 the big chunks are a
-// multiple of the persistent blocks in number, each <= max_chunk positions
-// (size ceil(main / (blocks m)), m = ceil(main / (blocks max_chunk))): every
-// block takes m of them.  A count just past a multiple (C4 at 2560: 534 big
-// chunks for 256 blocks) left a few blocks one big chunk behind the rest, a
-// tail the min_chunk phase was too small to hide (C4 485 vs 523 M samples/s
-// at 2560 vs 3072).  Chunk c holds the rays whose merged start lies in
-// [bound(c), bound(c+1)), so it is whole rays of at most max_chunk + K *
-// max_samples samples (possibly none).
-struct ChunkPlan {
-    int head_n, head, max_chunk, min_chunk, c1, n;
-    // first merged position of head chunk c (c <= head_n): head chunk c holds
-    // ~head (c + 1) / head_n positions, a ramp from ~0 to head
-    __host__ __device__ int hbound(int c) const {
-        return head_n > 0 ? (int)(((int64_t)head * c * (c + 1)) / (2 * (int64_t)head_n)) : 0;
-    }
-    __host__ __device__ int bound(int c) const {
-        const int H = hbound(head_n);
-        if (c < head_n) return hbound(c);
-        if (c <= c1) return H + (c - head_n) * max_chunk;
-        return H + (c1 - head_n) * max_chunk + (c - c1) * min_chunk;
-    }
-};
-
-// head_n chunks ramping from ~0 to `head` samples first (one per block): the
-// blocks' first MLP phases end at staggered times, so the walks' requests
-// reach the memory-side atomic units spread out instead of all at once after
-// one full chunk's MLP phase, and the blocks stay out of phase after.  A ramp
-// to max_chunk: C3 1183.4 -> 1189.2 M samples/s (field_bwd 2.995 -> 2.973
-// ms), C2 853.7 -> 862.3; head chunks of one size (rounds 2 and 5) changed
-// nothing, and at scale 16 a ramp to max_chunk / 2 lost 2-5 % (the big chunks,
-// only ~2 per block there, get shorter); profiles/r06/headramp/.  Then
-// max_chunk up to 15/16 of the work, then min_chunk (round 6: a tail of 1/16
-// instead of 1/8, with its chunks sized by shape on the host: C3 1191 -> 1194,
-// C4 653 -> 658, C5 789 -> 791; no tail at all lost 1 %; profiles/r06/tail/)
-__host__ __device__ __forceinline__ ChunkPlan chunk_plan(int total, int head_n, int head,
-                                                         int max_chunk, int min_chunk, int blocks) {
-    ChunkPlan p;
-    p.head = head; p.max_chunk = max_chunk; p.min_chunk = min_chunk;
-#ifndef RN_TAIL_SHIFT              // (timing studies: -D overrides the tail's share, 2^-shift)
-#define RN_TAIL_SHIFT 4
-#endif
-    const int main_end = total - (RN_TAIL_SHIFT < 31 ? total >> RN_TAIL_SHIFT : 0);
-    // the ramp takes ~head (head_n + 1) / 2 positions: none if that is past the main part
-    p.head_n = head > 0 && (int64_t)head * (head_n + 1) / 2 <= main_end ? head_n : 0;
-    const int H = p.hbound(p.head_n);
-    if (blocks > 0 && main_end > H) {
-        const int64_t main = main_end - H, per = (int64_t)blocks * max_chunk;
-        const int64_t m = (main + per - 1) / per;
-        const int64_t sz = (main + (int64_t)blocks * m - 1) / ((int64_t)blocks * m);
-        p.max_chunk = (int)(sz < min_chunk ? min_chunk : (sz > max_chunk ? max_chunk : sz));
-    }
-    p.c1 = p.head_n + (main_end > H ? (main_end - H) / p.max_chunk : 0);
-    const int rest = total - p.bound(p.c1);
-    p.n = p.c1 + (rest > 0 ? (rest + min_chunk - 1) / min_chunk : 0);
-    return p;
-}
-
-__global__ void __launch_bounds__(256)
-k_bwd_chunks(int B, int K, const int32_t* __restrict__ mstart,
-             const int32_t* __restrict__ offsets, const int32_t* __restrict__ seg_base,
-             const int32_t* __restrict__ seg_count, int head_n, int head, int max_chunk,
-             int min_chunk, int blocks, int cap_chunks, int32_t* __restrict__ chunk_first,
-             int32_t* __restrict__ desc, int32_t* __restrict__ queue) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int total = mstart[B];
-    const ChunkPlan p = chunk_plan(total, head_n, head, max_chunk, min_chunk, blocks);
-    const int n = min(p.n, cap_chunks);
-    if (c == 0) { queue[0] = 0; queue[1] = n; queue[2] = 0; }
-    if (c > n) return;
-    if (c == n) { chunk_first[c] = B; return; }
-    // first ray with mstart >= bound, for this chunk and the next
-    int first[2];
-    for (int e = 0; e < 2; ++e) {
-        if (c + e == n) { first[e] = B; continue; }
-        const int bound = p.bound(c + e);
-        int lo = 0, hi = B;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (mstart[mid] < bound) lo = mid + 1; else hi = mid;
-        }
-        first[e] = lo;
-    }
-    chunk_first[c] = first[0];
-    // descriptor: the chunk's sample range per model (the blocks read it with
-    // one 80-B load per ticket)
-    int32_t* d = desc + (size_t)c * CH_DESC;
-    const int r0 = first[0], r1 = first[1];
-    d[0] = r0; d[1] = r1; d[2] = 0; d[3] = 0;
-    for (int k = 0; k < MB_KMAX; ++k) {
-        int a0 = 0, cnt = 0;
-        if (k < K && r0 < B) {
-            a0 = offsets[k * B + r0];
-            const int a1 = r1 < B ? offsets[k * B + r1] : seg_base[k] + seg_count[k];
-            cnt = a1 - a0;
-        }
-        d[4 + k] = a0; d[4 + MB_KMAX + k] = cnt;
-    }
-}
-
 // dst[k][i] = idx[i] >= 0 ? f16(src[k][idx[i]]) : 0
 __global__ void __launch_bounds__(256)
 k_pack_f16(int64_t n, int K, int64_t src_stride, int64_t dst_stride, const float* __restrict__ src,
@@ -2541,29 +1504,7 @@ k_to_f16(int64_t n, const float* __restrict__ src, rn_half* __restrict__ dst) {
     dst[i] = (rn_half)src[i];
 }
 
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
-
 }  // namespace
-
-// The part of FieldArgs every field entry fills alike: the box, the hash-grid
-// level table (offsets/hsize/res/scale: 16 entries each), the f16 grid, the
-// MLP fragments and the ablation flags (after the entry's own checks).
-static void field_args_grid(FieldArgs& a, const void* grid_f16, const uint32_t* level_offset,
-                            const uint32_t* level_hsize, const uint32_t* level_res,
-                            const float* level_scale, const float* xyz_min, const float* extent,
-                            const void* frags) {
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.dbg = rn_dbg(g_field_dbg);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
-}
-
-// The same for the compact samples of the K models (ml_compact's segments).
-static void field_args_compact(FieldArgs& a, const float* ts, const int32_t* ray_of,
-                               const float* rays_o, const float* rays_d, const int32_t* seg_base,
-                               const int32_t* seg_count) {
-    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
-    a.seg_base = seg_base; a.seg_count = seg_count;
-}
 
 extern "C" {
 
@@ -2571,16 +1512,6 @@ void rn_set_debug_flags(int flags) { g_field_dbg = flags; }
 }  // extern "C"
 int rn_debug_flags_internal() { return rn_dbg(g_field_dbg); }   // 0 in librn.so
 extern "C" {
-
-int rn_set_level_pairing(uint64_t pairing) {
-    if (pairing != 0) {
-        uint32_t seen = 0;
-        for (int i = 0; i < 16; ++i) seen |= 1u << ((pairing >> (4 * i)) & 15u);
-        RN_CHECK_ARG(seen == 0xffffu, "pairing: every level exactly once");
-    }
-    g_level_pairing = pairing;
-    return 0;
-}
 
 /* ablation builds: read and clear the per-phase cycle counters (8 x u64) */
 int rn_debug_cycles(unsigned long long* out) {
@@ -2676,46 +1607,6 @@ int rn_field_bwd(const float* xyzs, const float* dirs, int64_t n_samples, const 
         if (feat_cache) k_field_bwd<1, CACHE_READ><<<grid, BWD_WAVES * 64, 0, (hipStream_t)stream>>>(a);
         else k_field_bwd<1, CACHE_NONE><<<grid, BWD_WAVES * 64, 0, (hipStream_t)stream>>>(a);
     }
-    RN_CHECK_LAUNCH();
-    return 0;
-}
-
-int rn_bwd_plan(const int32_t* counts, const int32_t* offsets, const int32_t* seg_base,
-                const int32_t* seg_count, const float* ts, int64_t n_rays, int32_t n_models,
-                int32_t head_chunks, int32_t head_size, int32_t max_chunk, int32_t min_chunk,
-                int32_t balance_blocks, int32_t cap_chunks, int32_t* mstart, int32_t* perm,
-                int32_t* chunk_first, int32_t* chunk_desc, int32_t* queue, const float* rays_o,
-                const float* rays_d, const float* xyz_min, const float* extent, float* prep,
-                void* stream) {
-    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1 && n_models <= MB_KMAX, "bad sizes");
-    RN_CHECK_ARG(max_chunk >= min_chunk && min_chunk >= 1 && cap_chunks >= 1 && head_chunks >= 0 &&
-                 head_size >= 0 && head_size <= max_chunk && balance_blocks >= 0,
-                 "bad chunk sizes");
-    RN_CHECK_ARG(counts && offsets && seg_base && seg_count && ts && mstart && perm &&
-                 chunk_first && chunk_desc && queue, "null pointer");
-    RN_CHECK_ARG(!prep || (rays_o && rays_d && xyz_min && extent), "null pointer (prep)");
-    PlanPrep P{};
-    P.prep = (float4*)prep; P.rays_o = rays_o; P.rays_d = rays_d;
-    if (prep) {
-        bool pow2 = true;
-        for (int c = 0; c < 3; ++c) {
-            P.mn[c] = xyz_min[c]; P.ext[c] = extent[c];
-            int e;
-            pow2 = pow2 && extent[c] > 0.f && std::frexp(extent[c], &e) == 0.5f &&
-                   e > -120 && e < 120;
-        }
-        for (int c = 0; c < 3; ++c) P.inv[c] = pow2 ? 1.0f / extent[c] : 0.f;
-    }
-    if (n_models > 2)
-        k_bwd_plan_multi<<<nblk(n_rays, PLANM_WAVES), PLANM_WAVES * 64, 0, (hipStream_t)stream>>>(
-            (int)n_rays, n_models, counts, offsets, seg_base, seg_count, ts, mstart, perm, P);
-    else
-        k_bwd_plan<<<nblk(n_rays, PLAN_WAVES), PLAN_WAVES * 64, 0, (hipStream_t)stream>>>(
-            (int)n_rays, n_models, counts, offsets, seg_base, seg_count, ts, mstart, perm, P);
-    RN_CHECK_LAUNCH();
-    k_bwd_chunks<<<nblk(cap_chunks + 1, 256), 256, 0, (hipStream_t)stream>>>(
-        (int)n_rays, n_models, mstart, offsets, seg_base, seg_count, head_chunks, head_size,
-        max_chunk, min_chunk, balance_blocks, cap_chunks, chunk_first, chunk_desc, queue);
     RN_CHECK_LAUNCH();
     return 0;
 }
@@ -2886,175 +1777,6 @@ int rn_field_bwd_merged_det(const float* ts, const int32_t* ray_of, const float*
                             dw_part, feat_cache, scratch, scratch_rows, park, max_chunk, blocks,
                             igrad_lo, igrad_carry, igrad_scale, nullptr, nullptr, nullptr, nullptr,
                             GM_F32, nullptr, nullptr, nullptr, 0, stream);
-}
-
-int rn_field_fwd_merged(const float* ts, const int32_t* ray_of, const float* rays_o,
-                        const float* rays_d, const int32_t* seg_base, const int32_t* seg_count,
-                        const int32_t* chunk_desc, int32_t* queue,
-                        int64_t n_rays, int32_t n_models, const void* grid_f16,
-                        const uint32_t* level_offset, const uint32_t* level_hsize,
-                        const uint32_t* level_res, const float* level_scale,
-                        const float* xyz_min, const float* extent, const void* frags,
-                        float* sigma, float* rgb, void* feat_cache, const int32_t* mstart,
-                        const int32_t* perm, int32_t blocks, int32_t threads, void* stream) {
-    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1 && n_models <= FM_KMAX && blocks >= 1,
-                 "bad sizes (n_models <= 8)");
-    RN_CHECK_ARG(threads >= 64 && threads <= 1024 && threads % 64 == 0, "threads: 64..1024, waves");
-    RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count &&
-                 chunk_desc && queue && grid_f16 && level_offset && level_hsize && level_res &&
-                 level_scale && xyz_min && extent && frags && sigma && rgb, "null pointer");
-    RN_CHECK_ARG(!(mstart || perm) || (mstart && perm && feat_cache),
-                 "merged-order encoding needs mstart, perm and the encoding cache");
-    FieldArgs a{};
-    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
-                    frags);
-    field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
-    a.sigma = sigma; a.rgb = rgb; a.feat = (rn_half*)feat_cache;
-    MergeArgs m{};
-    m.desc = chunk_desc; m.queue = queue;
-    m.mstart = mstart; m.perm = perm;
-    m.n_rays = (int)n_rays; m.n_models = n_models;
-    const bool gw = n_models > FM_LDS_K;
-    const size_t lds = gw ? 0 : (size_t)n_models * FIELD_FWD_FRAGS * RN_FRAG_BYTES;
-    hipStream_t st = (hipStream_t)stream;
-    RN_CHECK_HIP(hipMemsetAsync(queue + 2, 0, sizeof(int32_t), st), "ticket reset");
-#define RN_FM_LAUNCH(C, E)                                                                     \
-    do {                                                                                       \
-        if (gw) k_field_fwd_merged<C, E, true><<<blocks, threads, 0, st>>>(a, m);              \
-        else k_field_fwd_merged<C, E, false><<<blocks, threads, lds, st>>>(a, m);              \
-    } while (0)
-    if (mstart) RN_FM_LAUNCH(CACHE_WRITE, true);
-    else if (feat_cache) RN_FM_LAUNCH(CACHE_WRITE, false);
-    else RN_FM_LAUNCH(CACHE_NONE, false);
-#undef RN_FM_LAUNCH
-    RN_CHECK_LAUNCH();
-    return 0;
-}
-
-/* level-partitioned merged forward (k_enc_prep + k_field_encode_levels +
-   k_field_mlp_planes): the same outputs and encoding cache as
-   rn_field_fwd_merged with the merged-order encoding.  planes: 16 x
-   plane_stride u32 (plane_stride >= every sample index + 1); prep: 16 B per
-   merged sample; xq (optional probe): 96 int32, [8 g + x] += blocks of level
-   group g that ran on XCD x, then u64 [32 + g] first start and [40 + g] last
-   end of group g's blocks (s_memrealtime, 100 MHz). */
-int rn_field_fwd_levels(const float* ts, const int32_t* ray_of, const float* rays_o,
-                        const float* rays_d, const int32_t* seg_base, const int32_t* seg_count,
-                        int64_t n_rays, int32_t n_models, const void* grid_f16,
-                        const uint32_t* level_offset, const uint32_t* level_hsize,
-                        const uint32_t* level_res, const float* level_scale,
-                        const float* xyz_min, const float* extent, const void* frags,
-                        float* sigma, float* rgb, void* feat_cache, const int32_t* mstart,
-                        const int32_t* perm, uint32_t* planes, int64_t plane_stride, void* prep,
-                        int32_t prep_ready, int32_t enc_blocks, int32_t mlp_blocks, int32_t* xq,
-                        void* stream) {
-    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1 && n_models <= FM_KMAX && plane_stride >= 1,
-                 "bad sizes (n_models <= 8)");
-    RN_CHECK_ARG(enc_blocks >= 8 && enc_blocks % 8 == 0 && mlp_blocks >= 1,
-                 "bad launch (enc_blocks: a multiple of 8)");
-    RN_CHECK_ARG(ts && ray_of && rays_o && rays_d && seg_base && seg_count && grid_f16 &&
-                 level_offset && level_hsize && level_res && level_scale && xyz_min && extent &&
-                 frags && sigma && rgb && mstart && perm && planes && prep, "null pointer");
-    FieldArgs a{};
-    field_args_grid(a, grid_f16, level_offset, level_hsize, level_res, level_scale, xyz_min, extent,
-                    frags);
-    field_args_compact(a, ts, ray_of, rays_o, rays_d, seg_base, seg_count);
-    a.sigma = sigma; a.rgb = rgb; a.feat = (rn_half*)feat_cache;
-    a.planes = planes; a.plane_stride = plane_stride;
-    MergeArgs m{};
-    m.mstart = mstart; m.perm = perm; m.n_rays = (int)n_rays; m.n_models = n_models;
-    hipStream_t st = (hipStream_t)stream;
-    if (xq) {
-        RN_CHECK_HIP(hipMemsetAsync(xq, 0, 64 * sizeof(int32_t), st), "probe reset");
-        RN_CHECK_HIP(hipMemsetAsync(xq + 64, 0xff, 16 * sizeof(int32_t), st), "probe reset");
-        RN_CHECK_HIP(hipMemsetAsync(xq + 80, 0, 16 * sizeof(int32_t), st), "probe reset");
-    }
-    // (prep_ready: rn_bwd_plan wrote the per-position input as it placed the samples)
-    if (!prep_ready) k_enc_prep<<<1024, 256, 0, st>>>(a, m, (float4*)prep);
-    // level groups: (g, 15 - g) unless a study set another pairing (each level
-    // exactly once: checked on the host)
-    uint64_t pairing = g_level_pairing;
-    if (pairing == 0)
-        for (int g = 0; g < 8; ++g) pairing |= (uint64_t)(g | ((RN_L - 1 - g) << 4)) << (8 * g);
-    k_field_encode_levels<<<enc_blocks, 256, 0, st>>>(a, m, (const float4*)prep, xq, pairing);
-    k_field_mlp_planes<<<mlp_blocks, 1024,
-                         (size_t)min(n_models, FM_LDS_K) * FIELD_FWD_FRAGS * RN_FRAG_BYTES, st>>>(
-        a, n_models);
-    RN_CHECK_LAUNCH();
-    return 0;
-}
-
-int rn_seed_scale(const int32_t* seg_base, const int32_t* seg_count, int32_t n_models,
-                  const float* sigma, const float* dL_dsigma, const float* dL_drgb,
-                  uint32_t* work, float* scale, void* stream) {
-    RN_CHECK_ARG(n_models >= 1, "bad sizes");
-    RN_CHECK_ARG(seg_base && seg_count && sigma && dL_dsigma && dL_drgb && work && scale,
-                 "null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    RN_CHECK_HIP(hipMemsetAsync(work, 0, sizeof(uint32_t), st), "memset");
-    k_seed_max<<<dim3(256, n_models), 256, 0, st>>>(seg_base, seg_count, sigma, dL_dsigma,
-                                                     dL_drgb, work);
-    RN_CHECK_LAUNCH();
-    k_seed_scale<<<1, 1, 0, st>>>(work, scale);
-    RN_CHECK_LAUNCH();
-    return 0;
-}
-
-int rn_grid_fx_fold(const uint32_t* level_offset, const uint32_t* level_hsize,
-                    const uint32_t* level_res, int32_t* fx_acc, const float* fx_scale_cur,
-                    float* fx_scale_next, uint32_t* fx_vmax, int32_t* fx_redo, float* grid_grad,
-                    void* stream) {
-    RN_CHECK_ARG(level_offset && level_hsize && level_res && fx_acc && fx_scale_cur &&
-                 fx_scale_next && fx_vmax && fx_redo && grid_grad, "null pointer");
-    RN_CHECK_ARG(fx_scale_cur != fx_scale_next, "scale_cur and scale_next must differ");
-    GridMeta gm{};
-    uint32_t hashed = 0;
-    for (int l = 0; l < RN_L; ++l) {
-        gm.offset[l] = level_offset[l]; gm.hsize[l] = level_hsize[l]; gm.res[l] = level_res[l];
-        const uint64_t r = level_res[l];
-        if (r * r * r > (uint64_t)level_hsize[l]) hashed |= 1u << l;
-        RN_CHECK_ARG(level_offset[l] % 8 == 0, "level offsets must be multiples of 8 entries");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    FxStats* stats = reinterpret_cast<FxStats*>(fx_vmax);
-    k_fx_esum<<<dim3(128, RN_L), 256, 0, st>>>(gm, fx_scale_cur, fx_acc, grid_grad, stats);
-    k_fx_check<<<1, 64, 0, st>>>(hashed, fx_scale_cur, fx_scale_next, stats, fx_redo, nullptr, 0u);
-    RN_CHECK_LAUNCH();
-    {   // every level (dense ones go fixed point from their second step)
-        const int64_t e0 = 2 * (int64_t)level_offset[0];
-        const int64_t e1 = 2 * ((int64_t)level_offset[RN_L - 1] + level_hsize[RN_L - 1]);
-        RN_CHECK_ARG(e1 % 4 == 0, "table size must be a multiple of 2 entries");
-        const int64_t n4 = (e1 - e0) / 4;
-        const int nb = (int)std::min<int64_t>(2048, (n4 + 255) / 256);
-        k_fx_fold<<<nb > 0 ? nb : 1, 256, 0, st>>>(e0, e1, gm, fx_scale_cur, fx_acc, grid_grad,
-                                                    fx_redo);
-        RN_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-}  // extern "C"
-
-int rn_fx_check_binned(const float* fx_scale_cur, float* fx_scale_next, uint32_t* fx_stats,
-                       int32_t* fx_redo, const void* ctl, uint32_t pool_pages, void* stream) {
-    k_fx_check<<<1, 64, 0, (hipStream_t)stream>>>(0u, fx_scale_cur, fx_scale_next,
-                                                  reinterpret_cast<FxStats*>(fx_stats), fx_redo,
-                                                  (const GbCtl*)ctl, pool_pages);
-    RN_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" {
-
-int rn_igrad_to_f32(int64_t n, int32_t* igrad_lo, int32_t* igrad_carry, const float* scale,
-                    float* grid_grad, void* stream) {
-    RN_CHECK_ARG(n >= 0, "bad size");
-    if (n == 0) return 0;
-    RN_CHECK_ARG(igrad_lo && igrad_carry && scale && grid_grad, "null pointer");
-    k_igrad_to_f32<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(n, igrad_lo, igrad_carry, scale,
-                                                                   grid_grad);
-    RN_CHECK_LAUNCH();
-    return 0;
 }
 
 }  // extern "C"

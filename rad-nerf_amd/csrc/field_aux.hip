@@ -572,8 +572,6 @@ k_du_pack(DensityUpd u) {
     u.bitfields[k][b] = (uint8_t)bits;
 }
 
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
-
 // the launches of rn_density_update_sampled (VIS false) and
 // rn_density_update_visible (VIS true; u.count non-NULL selects the erode decay)
 template <bool VIS>

@@ -128,8 +128,6 @@ k_mark_invisible(MarkArgs a) {
     }
 }
 
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
-
 }  // namespace
 
 extern "C" {

@@ -13,7 +13,6 @@
 //    12 B sample record (t, dt, ray) instead of 32 B (xyz, dir, t, dt):
 //    xyz is recomputed bit-identically downstream as fmaf(t, d, o).
 #include "rn_march.h"
-#include "rn_bin.h"      // rn_debug_flags_internal
 #pragma clang fp contract(off)
 
 namespace {
@@ -470,8 +469,6 @@ k_ml_march_bw(int n_rays, int K, const int32_t* __restrict__ counts,
         gdir[3 * r] = d0; gdir[3 * r + 1] = d1; gdir[3 * r + 2] = d2;
     }
 }
-
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
 
 }  // namespace
 

@@ -184,8 +184,6 @@ k_ssim(int H, int W, int C, const float* __restrict__ pred, const float* __restr
     block_partial(wave_acc, work);
 }
 
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
-
 SsimWin gaussian_window() {
     // exp(-(d / sigma)^2 / 2) normalised to sum 1, formed in double
     double g[SS_WIN], s = 0.0;

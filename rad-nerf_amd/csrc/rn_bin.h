@@ -105,8 +105,7 @@ __host__ __device__ __forceinline__ int64_t gb_v1(uint64_t r) {
     return gb_decode((uint32_t)(r >> (GB_IDX_BITS + GB_V_BITS)));
 }
 
-int rn_debug_flags_internal();    // rn_set_debug_flags (field.hip), host side
-// k_fx_check in binned mode (field.hip): redo flag (record growth, pool
+// k_fx_check in binned mode (field_grad.hip): redo flag (record growth, pool
 // overflow) and the next step's scales
 int rn_fx_check_binned(const float* fx_scale_cur, float* fx_scale_next, uint32_t* fx_stats,
                        int32_t* fx_redo, const void* ctl, uint32_t pool_pages, void* stream);

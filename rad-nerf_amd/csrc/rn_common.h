@@ -29,6 +29,10 @@
 #define RN_ABL 0
 #endif
 __host__ __device__ constexpr int rn_dbg(int flags) { return RN_ABL ? flags : 0; }
+int rn_debug_flags_internal();    // rn_set_debug_flags' word (field.hip), host side; 0 in librn.so
+
+// host: blocks of t threads (or rows) that cover n
+inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
 
 // ---------------------------------------------------------------------------
 // status / error plumbing shared by every C-ABI entry point

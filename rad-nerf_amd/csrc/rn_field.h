@@ -1,6 +1,10 @@
-// Field device code shared by field.hip (forward / backward / merged kernels)
-// and field_aux.hip (input gradients, density-only evaluation): level tables,
-// the hash-grid encoder, SH, the MFMA MLP forward and the sample loaders.
+// Field device code shared by the field kernels' files -- field.hip (the
+// per-model forward / backward, the merged backward), field_fwd_merged.hip,
+// field_plan.hip, field_grad.hip (the rest of the fused path) and
+// field_aux.hip (input gradients, density-only evaluation): level tables, the
+// hash-grid encoder, SH, the MFMA MLP forward, the sample loaders and the
+// entries' FieldArgs filling.  The chunk plan's interface is rn_merge.h, the
+// grid-gradient forms' rn_gradform.h.
 // Reference: models/networks.py:229-328 (see field.hip header).
 #pragma once
 #include "rn_mlp.h"
@@ -609,6 +613,26 @@ int fill_args(FieldArgs& a, const float* xyz_min, const float* extent, const uin
         if (hsize[l] && (hsize[l] & (hsize[l] - 1u)) == 0) a.gm.pow2_mask |= 1u << l;
     }
     return 0;
+}
+
+// The part of FieldArgs every field entry fills alike: the box, the hash-grid
+// level table (offsets/hsize/res/scale: 16 entries each), the f16 grid, the
+// MLP fragments and the ablation flags (after the entry's own checks).
+static void field_args_grid(FieldArgs& a, const void* grid_f16, const uint32_t* level_offset,
+                            const uint32_t* level_hsize, const uint32_t* level_res,
+                            const float* level_scale, const float* xyz_min, const float* extent,
+                            const void* frags) {
+    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
+    a.dbg = rn_debug_flags_internal();
+    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+}
+
+// The same for the compact samples of the K models (ml_compact's segments).
+static void field_args_compact(FieldArgs& a, const float* ts, const int32_t* ray_of,
+                               const float* rays_o, const float* rays_d, const int32_t* seg_base,
+                               const int32_t* seg_count) {
+    a.ts = ts; a.ray_of = ray_of; a.rays_o = rays_o; a.rays_d = rays_d;
+    a.seg_base = seg_base; a.seg_count = seg_count;
 }
 
 }  // namespace

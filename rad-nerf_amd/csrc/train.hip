@@ -298,8 +298,6 @@ k_get_rays_pose_bw(int64_t n, const float* __restrict__ dirs, const float* __res
     }
 }
 
-inline int nblk(int64_t n, int t) { return (int)((n + t - 1) / t); }
-
 }  // namespace
 
 extern "C" {

@@ -25,7 +25,7 @@ MAX_SAMPLES = 1024
 NEAR_DISTANCE = 0.01
 SEG_ALIGN = 128
 FX_STATS_BYTES = 640      # include/radnerf.h RN_FX_STATS_BYTES
-# rn_field_bwd_merged's fx_mode, named as csrc/field.hip's GM_*: fp32 atomics
+# rn_field_bwd_merged's fx_mode, named as csrc/rn_gradform.h's GM_*: fp32 atomics
 # (exact integer with the integer triple), fixed point, the fp32 redo of a
 # flagged step, binned, binned with levels 0-7 by fp32 atomics ...
 GM_F32, GM_FX, GM_FX_REDO, GM_BIN, GM_BIN_F32 = 0, 2, 3, 4, 5
@@ -336,7 +336,7 @@ class FusedMLRenderer:
         # DESIGN §4)
         self.bin_f32_levels = (9 if model.size >= 8 else 8) if self.grid_bin else 0
         # the int32 form's wrap checksums weight gradient element i by 4 i
-        # (field.hip fx_weight), injective up to 2^28 elements: a larger table
+        # (rn_gradform.h fx_weight), injective up to 2^28 elements: a larger table
         # (none of the reference's configs: 16 levels x 2^19 entries x 2
         # features = 2^24) keeps fp32 atomics unless it is binned (no checksum)
         if not self.grid_bin and model.xyz_encoder.params.numel() > (1 << 28):

@@ -1,4 +1,4 @@
-"""CPU: the merged backward's chunk schedule (field.hip chunk_plan, restated
+"""CPU: the merged backward's chunk schedule (field_plan.hip chunk_plan, restated
 on the host in test_gpu_ml._chunk_bounds) never needs more chunk slots than
 include/radnerf.h's cap_chunks bound, which Workspace.chunk_list allocates
 (the old bound lacked the tail that the last big chunk can leave

@@ -229,7 +229,7 @@ def test_fx_per_entry_agreement(cuda, capsys, B, K, scale, f32_levels, bar):
 
 
 def _fx_weight(i):
-    return (4 * int(i)) & 0xFFFFFFFF                       # fx_weight (field.hip): byte offset
+    return (4 * int(i)) & 0xFFFFFFFF                       # fx_weight (rn_gradform.h): byte offset
 
 
 @pytest.mark.parametrize("wrapped", [True, False])

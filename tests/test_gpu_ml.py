@@ -359,7 +359,7 @@ def test_merged_backward_chunking(cuda):
 
 
 def _chunk_bounds(total, head_n, head, max_chunk, min_chunk, blocks):
-    """host restatement of field.hip chunk_plan: the merged-position bound of
+    """host restatement of field_plan.hip chunk_plan: the merged-position bound of
     every chunk (head chunks ramping from ~0 to head, big chunks over 15/16 of
     the work -- with blocks > 0 a multiple of blocks in number, each <=
     max_chunk -- then min_chunk)"""

@@ -151,7 +151,7 @@ def test_grid_record_e5m17_format():
 
 def test_fx_mode_refuses_grids_past_the_checksum_weights():
     """fx_mode 2's wrap checksums weight element i by its byte offset 4 i
-    (field.hip fx_weight), injective below 2^30: a grid of more than 2^28
+    (rn_gradform.h fx_weight), injective below 2^30: a grid of more than 2^28
     gradient elements is refused before any HIP call."""
     import numpy as np
     L = _lib.lib()
