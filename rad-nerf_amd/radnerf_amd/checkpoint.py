@@ -38,6 +38,8 @@ GEO_PADDED = [(64, 32), (32, 64)]
 RGB_PADDED = [(64, 32), (64, 64), (16, 64)]
 GATE_PADDED = [(64, 16), (64, 64), (64, 64), (64, 64), (16, 64)]
 MODEL_BUFFERS = ("center", "xyz_min", "xyz_max", "half_size", "grid_coords")
+# utils/util.py:36 keys_to_pop (the caller leaves `poses` out instead of popping it)
+SLIM_POPPED = ("directions", "model.density_grid", "model.grid_coords")
 
 
 def _split(vec, shapes, what):
@@ -141,9 +143,16 @@ def load_reference_state(model, gating_net=None, state=None, path=None):
 
 
 @torch.no_grad()
-def reference_state_dict(model, gating_net=None, dtype=torch.float16):
+def reference_state_dict(model, gating_net=None, dtype=torch.float16, slim=False, dR=None,
+                         dT=None, poses=None):
     """Export in the reference's key names and tcnn flat layouts (the inverse of
-    load_reference_state); tcnn keeps parameters in f16."""
+    load_reference_state); tcnn keeps parameters in f16.
+    dR / dT / poses: the Lightning module's own entries (train_ml.py:127-134),
+    top-level keys of its state_dict.  slim=True: what utils/util.py:33-43
+    (slim_ckpt) leaves and returns -- the flat state_dict without SLIM_POPPED's
+    keys, taken literally: 'model.density_grid' names no key of the
+    multi-model (its grids are model.density_grid_{i}) and those stay, while
+    the single NGP's grid goes; `poses` stays because it was given."""
     from .networks import NGP
     single = isinstance(model, NGP)
     nm = (lambda n, i: n) if single else (lambda n, i: f"{n}_{i}")
@@ -159,4 +168,11 @@ def reference_state_dict(model, gating_net=None, dtype=torch.float16):
     if gating_net is not None:
         sd["gating_net.encoder.params"] = _gate_to_tcnn(gating_net.params,
                                                         gating_net.out_dim).to(dtype)
+    for name, t in (("dR", dR), ("dT", dT), ("poses", poses)):
+        if t is not None:
+            sd[name] = t.detach().float().cpu().clone()
+    if slim:
+        for k in SLIM_POPPED:
+            sd.pop(k, None)
+        return sd
     return {"state_dict": sd}

@@ -414,7 +414,7 @@ class MNGP(nn.Module):
         c2w fp32 on the model's device (axes right / down / front); img_wh:
         (W, H).  Sets self.count_grid ((cascades, 128^3), the share of the
         cameras covering each cell: a plain attribute, not part of the
-        state_dict) and returns the per-cascade culled counts (int32 device
+        module's state_dict; Trainer.state_dict carries it) and returns the per-cascade culled counts (int32 device
         tensor).  Idempotent; call it again after loading a checkpoint."""
         Kh = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
         if Kh.shape != (3, 3):

@@ -11,8 +11,8 @@ background), one HIP launch per step (rn_sample_batch, csrc/sample.hip):
 
 Everything random is a counter-based hash of (seed, rank, step), stated in
 include/radnerf.h: no generator state, so a batch depends on its key alone,
-data-parallel ranks draw different pixels, and a resumed run continues the
-stream.  cosine_lr is the schedule of train_ml.py:148-151.
+data-parallel ranks draw different pixels, and a run resumed with its saved
+global_step (Trainer.load_state) continues the stream.  cosine_lr is the schedule of train_ml.py:148-151.
 """
 import math
 

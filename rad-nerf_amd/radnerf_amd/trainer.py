@@ -41,9 +41,10 @@ step_sampled draws the (image, pixel) picks, gathers the targets, forms the
 rays (refined by dR / dT under optimize_ext) and fills the march jitter and
 the random background in one launch, all from a counter-based hash of
 (seed, global_step, rank): no torch generator, different pixels on every
-rank, and a trainer resumed with the same seed and global_step continues the
-same stream of batches.  (The batches repeat; the step's gradients repeat bit
-for bit only with Trainer(deterministic=True), which replaces the step's fp32
+rank, and a trainer resumed by load_state / load_state_dict (which restore
+global_step with everything else) continues the same stream of batches.  (The
+batches repeat; the step's gradients repeat bit for bit only with
+Trainer(deterministic=True), which replaces the step's fp32
 sums in arrival order by ordered ones -- DESIGN.md §4 "Deterministic
 training".)  The consumed batch stays in `tr.last_batch`.  step and
 step_pixels keep drawing from torch's generator.  fit sets the cosine
@@ -65,14 +66,35 @@ skip the culled cells; `erode` decays cells seen by few cameras faster
 The cull uses the initial poses.  Under optimize_ext it is not repeated: the
 corrections move at lr 1e-8 and do not shift a frustum by a grid cell.
 
+The whole training state -- parameters, occupancy grids, pose corrections,
+Adam moments and step counts, global_step, fit's epoch position and log,
+torch's generator states -- is saved and restored by state_dict /
+load_state_dict and, through a file, save_state / load_state
+(radnerf_amd.train_state; Lightning's --ckpt_path and ModelCheckpoint).  With
+deterministic=True the continued run equals the uninterrupted one bit for bit:
+
+    tr.save_state("run/state.pt")                   # at any step
+    h = tr.save_state("run/state.pt", background=True); ...; h.wait()
+    tr2 = Trainer(...same arguments...); tr2.load_state("run/state.pt")
+    log = tr.fit_resumable(30, 1000, ckpt_dir="run", ckpt_every=5)
+    log = tr2.fit_resumable(30, 1000, ckpt_dir="run", resume=True)   # picks the run up
+
+(fit keeps its argument list and is fit_resumable without checkpoints.)
+
+export_reference / load_reference write and read the reference's slim
+checkpoint (utils/util.py:33-43), with dR / dT under optimize_ext.
+
 Out of scope: dataset file readers, the Lightning loop,
 logging back-ends.
 """
+import copy
 import math
+import os
 
 import torch
 
 from . import dist as rdist
+from . import train_state as TS
 from .fused import FusedMLRenderer
 from .optim import FusedAdam
 
@@ -85,9 +107,17 @@ def _rank():
     return td.get_rank() if td.is_available() and td.is_initialized() else 0
 
 
+def _world():
+    """torch.distributed's world size when it is initialised, else 1"""
+    import torch.distributed as td
+    return td.get_world_size() if td.is_available() and td.is_initialized() else 1
+
+
 class Trainer:
     # fit(): where its validations write their images (validate's save_dir); None: nowhere
     val_save_dir = None
+    # fit_resumable(ckpt_dir=...): write the checkpoints with save_state(background=True)
+    ckpt_background = True
 
     def __init__(self, model, gating_net, n_rays, lr=1e-2, lambda_opacity=1e-3,
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
@@ -186,6 +216,10 @@ class Trainer:
             # and apex's default eps (the network's 1e-15 is passed explicitly)
             groups.append(dict(params=pose_params, lr=pose_lr, eps=1e-8))
         self.opt = FusedAdam(groups, lr=lr, eps=1e-15)      # train_ml.py:143
+        self.pose_lr = float(pose_lr)
+        # fit's epoch position and log while it runs (state_dict's "progress");
+        # the background save's buffers and writer (save_state)
+        self._fit_progress = self._saver = None
         self.update_interval, self.warmup_steps, self.seed = update_interval, warmup_steps, seed
         # Adam as the epilogue of a bucketed all-reduce (dist.GradAllReduce.
         # reduce_and_step); False: one collective, a division, then Adam
@@ -236,7 +270,9 @@ class Trainer:
         under optimize_ext), march jitter, random background in one launch --
         then the step of step_pixels.  `noise` overrides the sampled jitter.
         The consumed batch is kept as self.last_batch (its buffers are reused
-        by the next call)."""
+        by the next call).  The key is all the stream depends on: a trainer
+        restored by load_state / load_state_dict has the saved global_step and
+        draws the batches the saved run would have drawn next."""
         from .sampler import sample_batch
         if self.images is None:
             raise ValueError("Trainer.step_sampled needs Trainer(images=..., directions=..., "
@@ -293,6 +329,233 @@ class Trainer:
             self.opt.step()
         self.global_step += 1
         return terms
+
+    # ------------------------------------------------------- the training state
+    def _named_params(self):
+        """the optimiser's parameters under the names the state files them by"""
+        out = [("xyz_encoder.params", self.model.xyz_encoder.params),
+               ("mlp_params", self.model.mlp_params), ("gating_net.params", self.gate.params)]
+        if self.optimize_ext:
+            out += [("dR", self.dR), ("dT", self.dT)]
+        return out
+
+    def _structure(self):
+        """What a state must match exactly.  The world size counts: the batch
+        stream is a function of the rank."""
+        m = self.model
+        return {"K": int(m.size), "scale": float(m.scale), "cascades": int(m.cascades),
+                "grid_size": int(m.grid_size), "table_len": int(m.xyz_encoder.params.numel()),
+                "gate_out_dim": int(self.gate.out_dim), "gate_type": str(self.gate.type),
+                "optimize_ext": bool(self.optimize_ext),
+                "n_images": 0 if self.poses is None else int(self.poses.shape[0]),
+                "world_size": _world()}
+
+    def _hyper(self):
+        """What a state must match unless load_state(override=True)."""
+        h = {"n_rays": int(self.n_rays), "seed": int(self.seed),
+             "update_interval": int(self.update_interval),
+             "warmup_steps": int(self.warmup_steps), "lr0": float(self.lr0),
+             "pose_lr": float(self.pose_lr), "esf": float(self.esf),
+             "random_bg": bool(self.random_bg), "erode": bool(self.erode),
+             "deterministic": bool(self.deterministic)}
+        h.update({k: float(v) for k, v in self.lambdas.items()})
+        for i, g in enumerate(self.opt.param_groups):
+            h[f"adam.{i}.betas"] = [float(b) for b in g["betas"]]
+            h[f"adam.{i}.eps"] = float(g["eps"])
+        return h
+
+    def _build_state(self, fetch):
+        """The state without its header.  fetch(name, device tensor) -> the
+        host tensor that holds (state_dict) or will hold (a background save)
+        its values; everything else is read here, at the call."""
+        m = self.model
+        model = {name: fetch("model/" + name, p) for name, p in self._named_params()[:3]}
+        names = ["center", "xyz_min", "xyz_max", "half_size"]
+        for i in range(m.size):
+            names += [f"density_grid_{i}", f"density_bitfield_{i}"]
+        if getattr(m, "count_grid", None) is not None:
+            names.append("count_grid")
+        for name in names:
+            model[name] = fetch("model/" + name, getattr(m, name))
+        state = {"structure": self._structure(), "hyper": self._hyper(), "model": model}
+        if self.optimize_ext:
+            state["poses"] = {"dR": fetch("poses/dR", self.dR), "dT": fetch("poses/dT", self.dT)}
+        per_param = {}
+        for name, p in self._named_params():
+            st = self.opt.state.get(p) or {}
+            per_param[name] = {"step": int(st.get("step", 0))}
+            for mom in ("exp_avg", "exp_avg_sq"):
+                t = st[mom] if mom in st else torch.zeros_like(p)
+                per_param[name][mom] = fetch(f"optimizer/{name}/{mom}", t)
+        state["optimizer"] = {"state": per_param,
+                              "groups": [{"lr": float(g["lr"])} for g in self.opt.param_groups]}
+        state["progress"] = {"global_step": int(self.global_step)}
+        fit = getattr(self, "_fit_progress", None)
+        if fit is not None:
+            state["progress"]["fit"] = copy.deepcopy(fit)
+        # step / step_pixels without `noise`, and _bg() under random_bg, draw from these
+        state["generators"] = {"cpu": torch.get_rng_state().clone()}
+        if self.device.type == "cuda":
+            state["generators"]["device"] = torch.cuda.get_rng_state(self.device).clone()
+        return state
+
+    def state_dict(self):
+        """The whole training state (radnerf_amd.train_state): a nested dict
+        of CPU tensors and plain int / float / str / bool / list / dict values
+        and nothing else, sealed with a header of per-tensor sizes and
+        checksums.  The renderer's workspaces and plans, the fixed-point
+        scales, the f16 table mirror, the packed fragments, the evaluator and
+        last_batch are not part of it: they are rebuilt."""
+        return TS.seal(self._build_state(lambda name, t: t.detach().to("cpu", copy=True)))
+
+    def load_state_dict(self, state, override=False):
+        """Restore the trainer from a state_dict().  Checked before anything is
+        touched: the header and every tensor's checksum; the structure (K,
+        scale, cascades, grid and table sizes, gate, optimize_ext and the
+        number of images, world size), which must match; the hyper-parameters,
+        which must match unless `override` (this trainer's then stand).  Each
+        failure is a ValueError listing what differs with both values.
+        Parameters are written in place, so the f16 mirror and the fragments
+        are remade from the loaded fp32 values."""
+        self._load(state, override, "the state", verified=False)
+
+    def _load(self, state, override, where, verified):
+        self.wait_saves()
+        if not verified:
+            TS.verify(state, where)
+        TS.check_compatible(state, self._structure(), self._hyper(), override, where)
+        m, dev = self.model, self.device
+        copies, moments = [], []
+
+        def match(dst, src, name):
+            if not torch.is_tensor(src) or src.numel() != dst.numel() or src.dtype != dst.dtype:
+                raise ValueError(f"{where}: {name} is {tuple(getattr(src, 'shape', ()))} "
+                                 f"{getattr(src, 'dtype', None)}, this trainer's is "
+                                 f"{tuple(dst.shape)} {dst.dtype}")
+            return src.reshape(dst.shape)
+
+        try:
+            saved = state["model"]
+            names = ["center", "xyz_min", "xyz_max", "half_size"]
+            for i in range(m.size):
+                names += [f"density_grid_{i}", f"density_bitfield_{i}"]
+            for name, p in self._named_params()[:3]:
+                copies.append((p, match(p, saved[name], name)))
+            for name in names:
+                copies.append((getattr(m, name), match(getattr(m, name), saved[name], name)))
+            if self.optimize_ext:
+                for name in ("dR", "dT"):
+                    p = getattr(self, name)
+                    copies.append((p, match(p, state["poses"][name], name)))
+            per_param = state["optimizer"]["state"]
+            for name, p in self._named_params():
+                st = per_param[name]
+                moments.append((p, int(st["step"]), match(p, st["exp_avg"], name + ".exp_avg"),
+                                match(p, st["exp_avg_sq"], name + ".exp_avg_sq")))
+            lrs = [float(g["lr"]) for g in state["optimizer"]["groups"]]
+            if len(lrs) != len(self.opt.param_groups):
+                raise ValueError(f"{where}: {len(lrs)} optimiser groups, this trainer has "
+                                 f"{len(self.opt.param_groups)}")
+            count = saved.get("count_grid")
+            if count is not None and tuple(count.shape) != (m.cascades, m.grid_size ** 3):
+                raise ValueError(f"{where}: count_grid is {tuple(count.shape)}")
+            global_step = int(state["progress"]["global_step"])
+            gens = state["generators"]
+        except KeyError as e:
+            raise ValueError(f"{where}: the state has no {e.args[0]!r}") from e
+        # everything checked: write
+        with torch.no_grad():
+            for dst, src in copies:
+                dst.copy_(src.to(dev))              # in place: _param_key changes
+        m._set_box_host()
+        m.count_grid = None if count is None else count.to(dev, copy=True)
+        for p, step, avg, sq in moments:
+            self.opt.state[p] = {"step": step, "exp_avg": avg.to(dev, copy=True),
+                                 "exp_avg_sq": sq.to(dev, copy=True)}
+        for g, lr in zip(self.opt.param_groups, lrs):
+            g["lr"] = lr
+        self.global_step = global_step
+        self._fit_progress = copy.deepcopy(state["progress"].get("fit"))
+        torch.set_rng_state(gens["cpu"])
+        if dev.type == "cuda" and "device" in gens:
+            torch.cuda.set_rng_state(gens["device"], dev)
+        # rebuilt as at a fresh start: the batch buffers, the evaluator, and the
+        # fixed-point scales (zeros: the first step measures the records in fp32)
+        self.last_batch = self._evaluator = None
+        ws = getattr(getattr(self, "renderer", None), "ws", None)
+        if ws is not None:
+            ws._fx, ws.fx_i = None, 0
+
+    def save_state(self, path, background=False, _after=None):
+        """state_dict() into a file (torch.save; written under a temporary
+        name of the same directory, then os.replace).  Returns a handle whose
+        wait() gives the path once the file is in place.
+        background=True: the call copies the device state into a staging copy
+        on the training stream, queues its copy to reused pinned host buffers
+        on a side stream, hands checksums and writing to a writer thread, and
+        returns; the next step may run at once, and the file holds the state
+        at the call whatever ran after it.  A second save waits for the
+        first; wait_saves(), load_state and interpreter exit wait for a
+        pending write."""
+        self.wait_saves()
+        if not background:
+            handle = TS.SaveHandle(TS.write_file(self.state_dict(), path))
+            if _after is not None:
+                _after()
+            return handle
+        if getattr(self, "_saver", None) is None:
+            self._saver = TS.BackgroundSaver(self.device)
+        return self._saver.save(self._build_state, path, after=_after)
+
+    def wait_saves(self):
+        """Join the writer of a background save; raises what it raised."""
+        if getattr(self, "_saver", None) is not None:
+            self._saver.wait()
+
+    def load_state(self, path, override=False):
+        """load_state_dict from a save_state file, read with torch.load(...,
+        weights_only=True): nothing of the file is executed.  A wrong format
+        version, a truncated file or a tensor failing its checksum raises
+        ValueError naming the file (and the tensor)."""
+        self.wait_saves()
+        self._load(TS.read_file(path), override, str(path), verified=True)
+
+    def export_reference(self, path, save_poses=None):
+        """The reference's slim checkpoint (utils/util.py:33-43 of the
+        Lightning state_dict): checkpoint.reference_state_dict's keys without
+        model.grid_coords, flat, plus dR / dT under optimize_ext and, with
+        save_poses (None: optimize_ext, as train_ml.py calls slim_ckpt), the
+        training poses."""
+        from .checkpoint import reference_state_dict
+        ext = self.optimize_ext
+        save_poses = ext if save_poses is None else bool(save_poses)
+        if save_poses and self.poses is None:
+            raise ValueError("Trainer.export_reference(save_poses=True) needs Trainer(poses=...)")
+        sd = reference_state_dict(self.model, self.gate, slim=True,
+                                  dR=self.dR if ext else None, dT=self.dT if ext else None,
+                                  poses=self.poses if save_poses else None)
+        return TS.atomic_save(sd, path)
+
+    def load_reference(self, path):
+        """The inverse of export_reference (checkpoint.load_reference_state;
+        also a full Lightning checkpoint).  Where the file holds dR / dT they
+        are loaded too; the optimiser's state is left alone."""
+        from .checkpoint import load_reference_state
+        state = torch.load(path, map_location="cpu", weights_only=True)
+        sd = state["state_dict"] if "state_dict" in state else state
+        poses = {k: sd[k] for k in ("dR", "dT") if k in sd}
+        if poses:
+            if not self.optimize_ext or set(poses) != {"dR", "dT"}:
+                raise ValueError(f"{path}: holds the pose corrections {sorted(poses)}; this "
+                                 f"trainer has optimize_ext={self.optimize_ext}")
+            for k, v in poses.items():
+                if tuple(v.shape) != tuple(getattr(self, k).shape):
+                    raise ValueError(f"{path}: {k} is {tuple(v.shape)}, this trainer's is "
+                                     f"{tuple(getattr(self, k).shape)}")
+        load_reference_state(self.model, self.gate, state=state)
+        with torch.no_grad():
+            for k, v in poses.items():
+                getattr(self, k).copy_(v.to(self.device, torch.float32))
 
     def validate(self, poses, images, T_threshold=1e-4, save_dir=None, epoch=0, swap_rb=False,
                  hard_gate=False):
@@ -353,6 +616,15 @@ class Trainer:
 
     def fit(self, num_epochs=30, steps_per_epoch=1000, val_poses=None, val_images=None,
             val_every=None, eta_min=None, callback=None):
+        """fit_resumable without checkpoints: the epoch loop from epoch 0 to
+        the end, nothing written, nothing loaded (the arguments and the
+        returned log are fit_resumable's)."""
+        return self.fit_resumable(num_epochs, steps_per_epoch, val_poses, val_images, val_every,
+                                  eta_min, callback)
+
+    def fit_resumable(self, num_epochs=30, steps_per_epoch=1000, val_poses=None, val_images=None,
+                      val_every=None, eta_min=None, callback=None, ckpt_dir=None,
+                      ckpt_every=None, keep=2, resume=False):
         """The epoch loop of train_ml.py:124-153,172-200,295-297 on the
         trainer's device-resident images.  At the start of epoch e the
         network's parameter group gets sampler.cosine_lr(lr, e, num_epochs,
@@ -369,9 +641,23 @@ class Trainer:
         With `val_save_dir` set on the trainer (None by default) each
         validation also writes its images there, named by the epoch (validate's
         save_dir and epoch).
-        The batches depend on (seed, global_step, rank) alone: a trainer
-        resumed with the same seed and global_step continues the stream."""
-        from .sampler import cosine_lr
+        The batches depend on (seed, global_step, rank) alone, so a run
+        resumed by fit_resumable(..., resume=...) (load_state underneath)
+        continues the stream.
+        ckpt_dir: rank 0 writes the whole training state there as
+        state_epochNNNN.pt (NNNN finished epochs) after every `ckpt_every`
+        epochs (None: val_every) and after the last, once the epoch's log
+        entry is complete and before the callback; in the background
+        (save_state(background=True)) unless `ckpt_background` is False on the
+        trainer.  Only the newest `keep` files stay.  The last write is waited
+        for before the call returns.
+        resume=True: load the newest complete file of ckpt_dir (none: start
+        fresh); resume=path: load that file.  The run continues at the saved
+        next epoch on the same schedule and returns the whole log, saved
+        entries included.  A num_epochs, steps_per_epoch or eta_min other than
+        the saved ones raises ValueError before anything is loaded or
+        rendered.  Under data parallelism every rank loads the same file and
+        no rank waits for another to save."""
         if self.images is None:
             raise ValueError("Trainer.fit needs Trainer(images=..., directions=..., poses=...)")
         num_epochs, steps = int(num_epochs), int(steps_per_epoch)
@@ -387,8 +673,52 @@ class Trainer:
             raise ValueError(f"Trainer.fit: val_every must be at least 1, got {val_every}")
         if callback is not None and not callable(callback):
             raise ValueError("Trainer.fit: callback must be callable")
-        log = []
-        for epoch in range(num_epochs):
+        if ckpt_every is not None and ckpt_dir is None:
+            raise ValueError("Trainer.fit_resumable: ckpt_every needs ckpt_dir, the directory the "
+                             "checkpoints are written to")
+        ckpt_every = val_every if ckpt_every is None else int(ckpt_every)
+        if ckpt_every < 1:
+            raise ValueError(f"Trainer.fit_resumable: ckpt_every must be at least 1, got "
+                             f"{ckpt_every}")
+        keep = int(keep)
+        if keep < 1:
+            raise ValueError(f"Trainer.fit_resumable: keep must be at least 1, got {keep}")
+        if resume is True and ckpt_dir is None:
+            raise ValueError("Trainer.fit_resumable(resume=True) needs ckpt_dir, the directory "
+                             "whose newest file is loaded (or resume=path)")
+        # as it is filed and compared: eta_min None is lr / 30 (sampler.cosine_lr)
+        mine = {"num_epochs": num_epochs, "steps_per_epoch": steps,
+                "eta_min": self.lr0 / 30 if eta_min is None else float(eta_min)}
+        log, first = [], 0
+        if resume:
+            found = TS.newest_checkpoint(ckpt_dir) if resume is True \
+                else (str(resume), TS.read_file(resume))
+            if found is not None:
+                path, state = found
+                saved = state.get("progress", {}).get("fit")
+                if saved is None:
+                    raise ValueError(f"{path}: holds no epoch position (it was not written by "
+                                     "fit_resumable); load it with load_state")
+                diff = TS.differences({k: saved.get(k) for k in mine}, mine)
+                if diff:
+                    raise ValueError(f"{path}: the call has another schedule -- "
+                                     + "; ".join(f"{k}: saved {u!r}, this call {v!r}"
+                                                 for k, u, v in diff))
+                self._load(state, False, path, verified=True)
+                first, log = int(saved["next_epoch"]), copy.deepcopy(saved["log"])
+        try:
+            self._fit_epochs(first, log, mine, steps, eta_min, val_poses, val_images, val_every,
+                             callback, ckpt_dir, ckpt_every, keep)
+        finally:
+            self._fit_progress = None       # absent outside fit
+            self.wait_saves()
+        return log
+
+    def _fit_epochs(self, first, log, mine, steps, eta_min, val_poses, val_images, val_every,
+                    callback, ckpt_dir, ckpt_every, keep):
+        from .sampler import cosine_lr
+        num_epochs = mine["num_epochs"]
+        for epoch in range(first, num_epochs):
             lr = cosine_lr(self.lr0, epoch, num_epochs, eta_min)
             self.opt.param_groups[0]["lr"] = lr
             names, acc = None, None
@@ -409,6 +739,12 @@ class Trainer:
                                     epoch=epoch)
                 entry["val"] = {k: float(val[k]) for k in ("psnr", "ssim")}
             log.append(entry)
+            self._fit_progress = dict(mine, next_epoch=epoch + 1, log=log)
+            if ckpt_dir is not None and _rank() == 0 and (
+                    (epoch + 1) % ckpt_every == 0 or epoch == num_epochs - 1):
+                os.makedirs(ckpt_dir, exist_ok=True)
+                self.save_state(os.path.join(ckpt_dir, TS.checkpoint_name(epoch + 1)),
+                                background=self.ckpt_background,
+                                _after=lambda: TS.prune(ckpt_dir, keep))
             if callback is not None:
                 callback(entry)
-        return log
