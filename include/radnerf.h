@@ -413,6 +413,64 @@ int rn_render_test(const float* rays_o, const float* rays_d, const float* hits_t
                    const void* frags, float T_threshold, float* opacity, float* depth,
                    float* rgb, int32_t* n_samples, int32_t blocks, void* stream);
 
+/* ---- gate-sparse test-time render --------------------------------------------
+ * The reference weights every sub-NeRF's render by the softmax gate
+ * (ml_rendering.py:33-36,65-68); Ray_Gate.forward returns a third value,
+ * top_k_indices, hard-wired to None (networks.py:1087-1093), so sparse gating
+ * was planned there and never built.  These two entries drop the (ray,
+ * sub-NeRF) pairs the gate has voted out before they are rendered.
+ *
+ * rn_gate_select.  gate (n_rays, K) fp32 row-major (rn_gate_fwd's rows), K =
+ * n_models <= 16; 0 <= gate_min < 1; 1 <= gate_topk <= K.  Pair (r, i) is LIVE
+ * iff gate[r,i] >= gate_min and fewer than gate_topk indices j have gate[r,j] >
+ * gate[r,i], or gate[r,j] == gate[r,i] with j < i (rank by gate descending,
+ * index ascending).  The first maximal gate of a row is live even below
+ * gate_min, so every ray keeps at least one sub-NeRF.  Written:
+ *   live (n_rays, K) uint8: 1 / 0;
+ *   gate_used (n_rays, K) fp32: gate[r,i] where live, exactly 0.0f otherwise;
+ *     with renormalize != 0, gate[r,i] / S_r where live, S_r the fp32 sum of the
+ *     row's live gates in index order and the division correctly rounded (a
+ *     row whose live gates are all 0 gives 0 / 0);
+ *   list [K][n_rays] int32: list[i][0 .. count[i]) are the rays live for
+ *     sub-NeRF i in ascending order; the tail is left as it was;  count [K];
+ *   the DEAD slots of opacity_k / depth_k [K][n_rays], rgb_k [K][n_rays][3] and
+ *     n_samples [K][n_rays] (rn_render_test's layouts) are set to 0; live slots
+ *     are left for rn_render_test_list.  All four NULL: no zero-fill.
+ * rn_ml_combine_test on the result with gate_used as its gate then adds an
+ * exact (0 + bg * 1) * 0 = 0 per dead pair.  Without renormalize the image
+ * differs from the dense one by at most the dead gate mass per ray: |d rgb_c|,
+ * |d opacity| <= sum over dead i of gate[r,i], plus rounding.
+ * List positions are ballot prefixes plus a scan of per-block counts, not
+ * arrival-order atomics: every output is a pure function of the arguments.  No
+ * host synchronisation.  n_rays == 0 zeroes count.  work: device scratch of
+ * RN_GATE_SELECT_WORK_BYTES (4-byte aligned), not shared by calls in flight on
+ * different streams.
+ *
+ * rn_render_test_list: rn_render_test for the listed pairs only.  The
+ * arguments and the grid (blocks, n_models) are rn_render_test's; sub-NeRF i
+ * renders rays list[i * n_rays + j], j < count[i], count read on the device,
+ * where the grid's blocks are also shared out among the sub-NeRFs in
+ * proportion to their counts (a sub-NeRF with most rays gets most blocks).
+ * A listed pair's opacity, depth, rgb and n_samples are rn_render_test's bits
+ * (one per-ray routine serves both kernels), in any list order; pairs not
+ * listed are not written; an entry outside [0, n_rays) is skipped.          */
+#define RN_GATE_SELECT_WORK_BYTES 65536
+int rn_gate_select(const float* gate, int64_t n_rays, int32_t n_models, float gate_min,
+                   int32_t gate_topk, int32_t renormalize, uint8_t* live, float* gate_used,
+                   int32_t* list, int32_t* count, float* opacity_k /*may be NULL*/,
+                   float* depth_k /*may be NULL*/, float* rgb_k /*may be NULL*/,
+                   int32_t* n_samples /*may be NULL*/, void* work, void* stream);
+int rn_render_test_list(const float* rays_o, const float* rays_d, const float* hits_t,
+                        int64_t n_rays, int32_t n_models, const uint8_t* density_bitfields,
+                        int64_t bitfield_bytes, int32_t cascades, float scale,
+                        float exp_step_factor, int32_t grid_size, int32_t max_samples,
+                        const void* grid_f16, const uint32_t* level_offset,
+                        const uint32_t* level_hsize, const uint32_t* level_res,
+                        const float* level_scale, const float* xyz_min, const float* extent,
+                        const void* frags, float T_threshold, float* opacity, float* depth,
+                        float* rgb, int32_t* n_samples, const int32_t* list,
+                        const int32_t* count, int32_t blocks, void* stream);
+
 /* Exact integer accumulation of the merged backward's grid gradient
  * (optional; igrad_lo == NULL keeps fp32 atomics into grid_grad).  With
  * igrad_lo / igrad_carry (int32, one per grid_grad element, zero on entry) and

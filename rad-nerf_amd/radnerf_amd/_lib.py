@@ -81,6 +81,10 @@ SIGNATURES = {
     "rn_grid_binned_fold": [P, P, P, P, P, P, P, P, I32, P, P, P, P, P, P],
     "rn_render_test": [P, P, P, I64, I32, P, I64, I32, F32, F32, I32, I32, P, P, P, P, P, P, P,
                        P, F32, P, P, P, P, I32, P],
+    # gate-sparse test-time render (sparse_gate.py, evaluate.py)
+    "rn_gate_select": [P, I64, I32, F32, I32, I32, P, P, P, P, P, P, P, P, P, P],
+    "rn_render_test_list": [P, P, P, I64, I32, P, I64, I32, F32, F32, I32, I32, P, P, P, P, P, P,
+                            P, P, F32, P, P, P, P, P, P, I32, P],
     "rn_seed_scale": [P, P, I32, P, P, P, P, P, P],
     "rn_igrad_to_f32": [I64, P, P, P, P, P],
     "rn_field_fwd_merged": [P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P, P, P, P, P, P, P,
@@ -122,6 +126,7 @@ SIGNATURES = {
 
 ABI_VERSION = 9
 METRICS_WORK_BYTES = 8192       # include/radnerf.h RN_METRICS_WORK_BYTES
+GATE_SELECT_WORK_BYTES = 65536  # include/radnerf.h RN_GATE_SELECT_WORK_BYTES
 _lib = None
 
 _CODE = {P: "p", I32: "i", I64: "l", F32: "f", F64: "d", U64: "u"}

@@ -16,11 +16,23 @@ writes background, gate-weighted rgb / opacity / depth and the per-sub-NeRF
 depths at the chunk's rows of the image-sized outputs.  The results are those
 of rendering.ml_render(test_time=True) on the same rays; everything runs on
 the current stream with no host synchronisation and no per-chunk allocation.
+
+Gate-sparse render (sparse_gate.py; include/radnerf.h rn_gate_select):
+render_image / evaluate take gate_min, gate_topk and renormalize.  With
+gate_min > 0 or gate_topk < K the chain is gate -> rn_gate_select ->
+rn_render_test_list (only the live (ray, sub-NeRF) pairs are rendered; the dead
+slots hold exact zeros) -> rn_ml_combine_test with gate_used for the gate.  The
+result gains gating_live (N, K) uint8, gating_used (N, K) fp32 and pairs (the
+number of live pairs, a device int64); depth_k is 0 at dead pairs,
+total_samples counts live pairs, gating_code stays the full softmax.  Without
+renormalize the image differs from the dense one by at most the dead gate mass
+per ray.  The defaults, K = 1 and gating_net=None run the dense launches above
+and return the dense dict.
 """
 import torch
 
-from . import imageout, metrics
-from ._lib import lib
+from . import imageout, metrics, sparse_gate
+from ._lib import GATE_SELECT_WORK_BYTES, lib
 from .rendering import MAX_SAMPLES, NEAR_DISTANCE
 
 DEFAULT_CHUNK = 1 << 18
@@ -100,6 +112,7 @@ class ImageEvaluator:
         # ml_rendering.py:149-153: white beyond the samples unless exp stepping
         self.bg = torch.ones(3, **f32) if self.esf == 0 else torch.zeros(3, **f32)
         self.out8 = None                                 # images8()'s buffers, on first use
+        self.sparse = None                               # the sparse render's, on first use
 
     def _bitfields(self):
         """[K][bytes] contiguous, as rn_render_test reads them (refreshed per
@@ -115,9 +128,31 @@ class ImageEvaluator:
             self.bits[i].copy_(b)
         return self.bits, bf[0].numel()
 
+    def _sparse_params(self, fn, gate_min, gate_topk, renormalize):
+        """None for the dense render (every pair live: the defaults, K = 1, no
+        gate), else (gate_min, gate_topk, renormalize) checked.  No library."""
+        K = self.model.size
+        tau, k = sparse_gate.check_params(fn, K, gate_min, gate_topk)
+        if self.gate is None or sparse_gate.is_dense(K, tau, k):
+            return None
+        return tau, k, int(bool(renormalize))
+
+    def _sparse_buffers(self):
+        if self.sparse is None:
+            K, N, B, dev = self.model.size, self.n_pix, self.chunk, self.device
+            self.sparse = {
+                "live": torch.empty(N, K, dtype=torch.uint8, device=dev),
+                "used": torch.empty(N, K, dtype=torch.float32, device=dev),
+                "list": torch.empty(K * B, dtype=torch.int32, device=dev),
+                "count": torch.empty(K, dtype=torch.int32, device=dev),
+                "work": torch.empty(GATE_SELECT_WORK_BYTES, dtype=torch.uint8, device=dev)}
+        return self.sparse
+
     @torch.no_grad()
-    def render_image(self, pose, T_threshold=1e-4, max_samples=MAX_SAMPLES):
+    def render_image(self, pose, T_threshold=1e-4, max_samples=MAX_SAMPLES, gate_min=0.0,
+                     gate_topk=None, renormalize=False):
         _check_pose("ImageEvaluator.render_image", pose)
+        sp = self._sparse_params("ImageEvaluator.render_image", gate_min, gate_topk, renormalize)
         m, g, dev, L = self.model, self.gate, self.device, lib()
         K, N = m.size, self.n_pix
         pose = pose.detach().to(dev, torch.float32).contiguous()
@@ -129,6 +164,9 @@ class ImageEvaluator:
         gfrags = None if g is None else g.packed_frags()
         out = self.out
         total = torch.zeros((), device=dev, dtype=torch.int64)
+        if sp is not None:
+            sb = self._sparse_buffers()
+            pairs = torch.zeros((), device=dev, dtype=torch.int64)
         ptr = lambda t: None if t is None else t.data_ptr()
         for ray0 in range(0, N, self.chunk):
             n = min(self.chunk, N - ray0)
@@ -150,13 +188,28 @@ class ImageEvaluator:
                                  self.hit_idx.data_ptr(), st)
             near = self.hits_t[:n, 0, 0]
             near.masked_fill_((near >= 0) & (near < NEAR_DISTANCE), NEAR_DISTANCE)
-            L.render_test(self.rays_o.data_ptr(), self.rays_d.data_ptr(), self.hits_t.data_ptr(),
-                          n, K, bits.data_ptr(), nb, m.cascades, float(m.scale), self.esf,
-                          m.grid_size, int(max_samples), grid16.data_ptr(), lo, lh, lr, ls,
-                          m._h_min.ctypes.data, m._h_ext.ctypes.data, frags.data_ptr(),
-                          float(T_threshold), self.op_k.data_ptr(), self.depth_k.data_ptr(),
-                          self.rgb_k.data_ptr(), self.n_smp.data_ptr(),
-                          max(1, min((n + 3) // 4, 512 // K)), st)
+            render = (self.rays_o.data_ptr(), self.rays_d.data_ptr(), self.hits_t.data_ptr(),
+                      n, K, bits.data_ptr(), nb, m.cascades, float(m.scale), self.esf,
+                      m.grid_size, int(max_samples), grid16.data_ptr(), lo, lh, lr, ls,
+                      m._h_min.ctypes.data, m._h_ext.ctypes.data, frags.data_ptr(),
+                      float(T_threshold), self.op_k.data_ptr(), self.depth_k.data_ptr(),
+                      self.rgb_k.data_ptr(), self.n_smp.data_ptr())
+            blocks = max(1, min((n + 3) // 4, 512 // K))
+            if sp is None:
+                L.render_test(*render, blocks, st)
+            else:
+                # the dead slots of the per-pair buffers become zeros, the live
+                # ones are rendered: the combine then adds exact zeros
+                used_ptr = sb["used"].data_ptr() + 4 * K * ray0
+                L.gate_select(gate_ptr, n, K, sp[0], sp[1], sp[2],
+                              sb["live"].data_ptr() + K * ray0, used_ptr, sb["list"].data_ptr(),
+                              sb["count"].data_ptr(), self.op_k.data_ptr(),
+                              self.depth_k.data_ptr(), self.rgb_k.data_ptr(),
+                              self.n_smp.data_ptr(), sb["work"].data_ptr(), st)
+                L.render_test_list(*render, sb["list"].data_ptr(), sb["count"].data_ptr(),
+                                   blocks, st)
+                pairs += sb["count"].sum()
+                gate_ptr = used_ptr
             L.ml_combine_test(gate_ptr, self.op_k.data_ptr(), self.depth_k.data_ptr(),
                               self.rgb_k.data_ptr(), self.bg.data_ptr(), n, K, ray0,
                               out["rgb"].data_ptr(), out["opacity"].data_ptr(),
@@ -164,11 +217,15 @@ class ImageEvaluator:
             total += self.n_smp[:K * n].sum()
         res = dict(out)
         res["total_samples"] = total
+        if sp is not None:
+            res["gating_live"], res["gating_used"], res["pairs"] = sb["live"], sb["used"], pairs
         return res
 
-    def evaluate(self, pose, rgb_gt, T_threshold=1e-4, max_samples=MAX_SAMPLES):
+    def evaluate(self, pose, rgb_gt, T_threshold=1e-4, max_samples=MAX_SAMPLES, gate_min=0.0,
+                 gate_topk=None, renormalize=False):
         """validation_step's two numbers for one image: rgb_gt (H*W, 3) fp32
-        on the device -> {"psnr", "ssim"} (device fp64 scalars)."""
+        on the device -> {"psnr", "ssim"} (device fp64 scalars).  gate_min /
+        gate_topk / renormalize: the gate-sparse render, as render_image."""
         fn = "ImageEvaluator.evaluate"
         if not torch.is_tensor(rgb_gt) or tuple(rgb_gt.shape) != (self.n_pix, 3):
             raise ValueError(f"{fn}: rgb_gt must be a ({self.n_pix}, 3) tensor, got "
@@ -176,7 +233,8 @@ class ImageEvaluator:
         # dtype, contiguity and the 11 x 11 window, before anything is rendered
         metrics._check_image(fn, rgb_gt, rgb_gt, self.img_wh)
         _check_pose("ImageEvaluator.evaluate", pose)
-        rgb = self.render_image(pose, T_threshold, max_samples)["rgb"]
+        rgb = self.render_image(pose, T_threshold, max_samples, gate_min, gate_topk,
+                                renormalize)["rgb"]
         return {"psnr": metrics.psnr(rgb, rgb_gt), "ssim": metrics.ssim(rgb, rgb_gt, self.img_wh)}
 
     def images8(self, swap_rb=False, hard_gate=False):

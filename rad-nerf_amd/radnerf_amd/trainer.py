@@ -558,7 +558,7 @@ class Trainer:
                 getattr(self, k).copy_(v.to(self.device, torch.float32))
 
     def validate(self, poses, images, T_threshold=1e-4, save_dir=None, epoch=0, swap_rb=False,
-                 hard_gate=False):
+                 hard_gate=False, gate_min=0.0, gate_topk=None, renormalize=False):
         """validation_step (train_ml.py:214-250) over (pose, image) pairs:
         poses (N, 3, 4) camera-to-world, used as they are (the test split's own
         poses: no dR / dT, as the reference), images (N, H*W, 3) fp32 (or a
@@ -572,7 +572,10 @@ class Trainer:
         and blue exchanged, as the reference's files) and, with more than one
         sub-NeRF, the gate map as `..._g.png` (ImageEvaluator.images8,
         imageout.ImageSaver); the files are complete on return, the numbers
-        are the same.  Without it nothing more is launched or allocated."""
+        are the same.  Without it nothing more is launched or allocated.
+        gate_min / gate_topk / renormalize: the gate-sparse render of
+        ImageEvaluator.render_image (sparse_gate.py); the defaults render every
+        sub-NeRF on every ray."""
         from .evaluate import ImageEvaluator
         from .metrics import ImageMetrics
         if self.directions is None or self.img_wh is None:
@@ -603,7 +606,9 @@ class Trainer:
         acc = ImageMetrics()
         for i, (pose, im) in enumerate(zip(poses, images)):
             im = im.to(self.device)
-            rgb = self._evaluator.render_image(pose, T_threshold)["rgb"]
+            rgb = self._evaluator.render_image(pose, T_threshold, gate_min=gate_min,
+                                               gate_topk=gate_topk,
+                                               renormalize=renormalize)["rgb"]
             acc.update(rgb, im, self.img_wh)
             if saver is not None:
                 im8 = self._evaluator.images8(swap_rb=swap_rb, hard_gate=hard_gate)
