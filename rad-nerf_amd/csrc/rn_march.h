@@ -129,11 +129,14 @@ __device__ __forceinline__ bool march_query(float t, float ox, float oy, float o
 // queried (the chain) and emitted.  The wave evaluates 64 consecutive t_k per
 // chunk (lane j: t_{base+j}, the same float additions in the same order),
 // queries all of them in parallel (one bitfield load per lane instead of one
-// dependent load per step), and then walks the chain through the chunk with
-// scalar ops: next(k) = k + 1 if occupied, else the first k' > k with
-// t_k' >= target(k) (the do-while of :228-230).  The chain is the reference's
-// sequence of queries, so counts and samples are identical; the serial
-// latency per step drops from a dependent L2 load to a few scalar ops.
+// dependent load per step), and then walks the chain through the chunk:
+// next(k) = k + 1 if occupied, else the first k' > k with t_k' >= target(k)
+// (the do-while of :228-230).  Every lane works out its own link of that
+// chain in the vector lanes (a CU has four vector pipes and one scalar unit,
+// which the walk used to saturate); the scalar part only hops from link to
+// link.  The chain is the reference's sequence of queries, so counts and
+// samples are identical; the serial latency per step drops from a dependent
+// L2 load to a few lane reads.
 // NEG: march from a negative t1 too (the test-time march, raymarching.cu:
 // 364-365, starts wherever hits_t says; the training march requires t1 >= 0)
 template <bool WRITE, typename Sink, bool NEG = false>
@@ -187,42 +190,60 @@ __device__ int march_ray_wave(float ox, float oy, float oz, float dx, float dy, 
                                      x, y, z, dt, target) && alive;
         const uint64_t alive_m = __builtin_amdgcn_ballot_w64(alive);
         const uint64_t occ_m = __builtin_amdgcn_ballot_w64(occ);
-        // walk the chain through this chunk (scalar).  A run of occupied steps
-        // is on the chain as a whole (next(k) = k + 1), so one iteration per
-        // run and one per empty query.
-        uint64_t mark = 0;
+        // Every lane's own link of the chain, in the vector lanes: the span of
+        // steps the chain marks when it visits this lane, and the lane it
+        // visits next (RN_WAVE: none in this chunk).
+        //   occupied: the run [lane, end) up to the first step that is not
+        //             occupied; next = end if that step is alive.
+        //   empty:    the step itself; next = the first alive step after it
+        //             with t >= target.  t does not decrease over the lanes
+        //             and the alive lanes are a prefix, so that is the lower
+        //             bound of target in key = alive ? t : +inf (no smaller
+        //             than lane + 1), found by a 6-probe binary search over
+        //             the lanes' own key values.  A target of +inf or NaN
+        //             finds no alive lane.
+        const uint64_t stop = ~occ_m & ~lt_mask;          // occupied lane: bit `lane` is clear
+        const uint64_t run = ((stop & (0ull - stop)) - 1ull) & ~lt_mask;      // steps [lane, end)
+        const int end = stop ? __builtin_ctzll(stop) : RN_WAVE;
+        const int key = __float_as_int(alive ? t : INFINITY);
+        int lb = 0;                                       // lanes [0, lb) have key < target
+#pragma unroll
+        for (int h = RN_WAVE / 2; h > 0; h >>= 1) {
+            const float kv = __int_as_float(__builtin_amdgcn_ds_bpermute((lb + h - 1) << 2, key));
+            lb += kv >= target ? 0 : h;
+        }
+        const float klast = __int_as_float(__builtin_amdgcn_readlane(key, RN_WAVE - 1));
+        lb += (lb == RN_WAVE - 1 && !(klast >= target)) ? 1 : 0;
+        const int to = occ ? end : max(lb, lane + 1);
+        const int link = (to < RN_WAVE && ((alive_m >> (to & (RN_WAVE - 1))) & 1ull)) ? to : RN_WAVE;
+        const uint64_t span = occ ? run : 1ull << lane;
+        const int span_lo = (int)(uint32_t)span, span_hi = (int)(uint32_t)(span >> 32);
+        // hop along the chain (scalar): three lane reads per chain element
         const uint64_t cand = __builtin_amdgcn_ballot_w64(alive && t >= need);
         int cur = cand ? __builtin_ctzll(cand) : RN_WAVE;
-        int emitted = 0;
-        bool full = false;
-        const bool capfree = n + RN_WAVE < cap;          // this chunk cannot reach the cap
+        int last = -1;
+        uint32_t mark_lo = 0, mark_hi = 0;
         while (cur < RN_WAVE) {
-            const uint64_t from = ~0ull << cur;
-            if ((occ_m >> cur) & 1ull) {
-                const uint64_t stop = ~occ_m & from;
-                const int end = stop ? __builtin_ctzll(stop) : RN_WAVE;
-                need = -INFINITY;
-                if (!capfree && n + emitted + (end - cur) >= cap) {
-                    const int e2 = cur + (cap - n - emitted);
-                    mark |= from & (e2 < RN_WAVE ? ~(~0ull << e2) : ~0ull);
-                    emitted += e2 - cur;
-                    full = true;
-                    break;
-                }
-                mark |= from & ((stop & (0ull - stop)) - 1ull);   // steps [cur, end)
-                emitted += end - cur;
-                cur = (end < RN_WAVE && ((alive_m >> end) & 1ull)) ? end : RN_WAVE;
-            } else {
-                mark |= 1ull << cur;
-                need = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(target), cur));
-                const uint64_t nxt = __builtin_amdgcn_ballot_w64(alive && t >= need) & (from << 1);
-                cur = nxt ? __builtin_ctzll(nxt) : RN_WAVE;
-            }
+            mark_lo |= (uint32_t)__builtin_amdgcn_readlane(span_lo, cur);
+            mark_hi |= (uint32_t)__builtin_amdgcn_readlane(span_hi, cur);
+            last = cur;
+            cur = __builtin_amdgcn_readlane(link, cur);
         }
-        const uint64_t emit_m = mark & occ_m;
-        if (WRITE && ((emit_m >> lane) & 1ull))
-            sink.emit(start + n + __builtin_popcountll(emit_m & lt_mask), x, y, z, t, dt);
-        n += __builtin_popcountll(emit_m);
+        // the next chunk resumes right after an occupied run, or at the last
+        // empty query's target
+        if (last >= 0)
+            need = ((occ_m >> last) & 1ull)
+                       ? -INFINITY
+                       : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(target), last));
+        // the cap: the first cap - n marked occupied steps are emitted and the
+        // ray ends there (raymarching.cu:204); nothing after them is observable
+        const uint64_t emit_m = ((uint64_t)mark_hi << 32 | mark_lo) & occ_m;
+        const int room = cap - n, found = __builtin_popcountll(emit_m);
+        const int before = __builtin_popcountll(emit_m & lt_mask);
+        const bool full = found >= room;
+        if (WRITE && ((emit_m >> lane) & 1ull) && before < room)
+            sink.emit(start + n + before, x, y, z, t, dt);
+        n += min(found, room);
         if (full || alive_m != ~0ull) break;            // cap reached, or the ray left [t1, t2)
         const float tl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), RN_WAVE - 1));
         tb = tl + rn_calc_dt(tl, c.esf, c.max_samples, c.grid_size, c.dt_scale);
