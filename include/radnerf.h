@@ -471,6 +471,72 @@ int rn_render_test_list(const float* rays_o, const float* rays_d, const float* h
                         float* rgb, int32_t* n_samples, const int32_t* list,
                         const int32_t* count, int32_t blocks, void* stream);
 
+/* ---- routed training (opt-in; DESIGN.md §4 "Routed training") ----------------
+ * The training step for the (ray, sub-NeRF) pairs rn_gate_select keeps, so the
+ * model that is trained is the model the gate-sparse render draws.  A DEAD pair
+ * is a pair with sample count 0 and gate_used exactly 0: every kernel after the
+ * march already handles pairs without samples (rays that miss the box), so
+ * rn_scan_segments, rn_ml_compact, rn_bwd_plan, the field forwards / backwards,
+ * the composites and rn_ml_march_bw run unchanged on the counts written here.
+ *
+ * rn_ml_march_count_list: rn_ml_march_count's arguments, then list [K][n_rays]
+ * and count [K] in rn_gate_select's layouts (K = n_models <= 16; count is read
+ * on the device, no host read).  The entry first zeroes counts [K][n_rays] on
+ * the stream, then marches one wave per listed pair: wave w of the launch takes
+ * flat pair w -- the running sum of count[] gives sub-NeRF k, list[k][w - sum]
+ * the ray r -- so the live work is dense at the front of the grid and waves past
+ * sum(count) leave at once.  Pair (k, r) gets counts[k][r] and the staging slot
+ * (k*n_rays + r)*max_samples with rn_ml_march_count's bits (the same AABB test,
+ * near clamp, jitter noise[k*n_rays + r] and per-ray march), whatever the order
+ * of the list.  A pair not listed keeps count 0 and its staging slot is not
+ * written.  An entry outside [0, n_rays) is skipped; count[k] is clamped to
+ * [0, n_rays]; a pair listed twice is marched twice with the same result.
+ *
+ * rn_gate_select_bw: the backward of gate_used = rn_gate_select(gate) with the
+ * selection (live) held constant -- the selection itself has no gradient.
+ * gate, live as rn_gate_select read / wrote them; dL_dgate_used (n_rays, K) is
+ * what rn_ml_combine_bw writes, which is non-zero on dead pairs (bg . dL_drgb)
+ * and is masked here.  dL_dgate (n_rays, K), which may be dL_dgate_used itself:
+ *   dead pair: exactly 0;
+ *   live, renormalize == 0: dL_dgate_used[r,i];
+ *   live, renormalize != 0: (d_i - D) / S with S the fp32 sum of the row's live
+ *     gates in index order (rn_gate_select's S), u_j = gate_j / S correctly
+ *     rounded, D the fp32 sum in index order, from 0, over live j of the rounded
+ *     products d_j * u_j, no contraction, the final division correctly rounded;
+ *     a row with S == 0 gives 0.
+ * One lane per ray, no atomics: a pure function of the arguments.
+ *
+ * rn_nerf_loss_routed / rn_nerf_loss_routed_det: rn_nerf_loss / rn_nerf_loss_det
+ * with gate_used in place of gate and live (n_rays, K) uint8.  A dead pair adds
+ * nothing to the depth-mutual sum and gets dL_ddepth = 0; the row's mean depth
+ * is sum_k depth * gate_used; the divisor stays B K, so with every pair live
+ * and gate_used == gate the results are the dense entries' bit for bit.
+ * importance is still the FULL softmax gate's column sums (the reference's
+ * gating_importance, the term that keeps the routing balanced), and dL_dgate
+ * its seed on the softmax gate -- add it after rn_gate_select_bw.            */
+int rn_ml_march_count_list(const float* rays_o, const float* rays_d, const float* center,
+                           const float* half_size, float near_distance, const float* noise,
+                           const uint8_t* density_bitfields, int64_t bitfield_bytes,
+                           int32_t n_models, int32_t cascades, float scale, float exp_step_factor,
+                           int32_t grid_size, int32_t max_samples, int64_t n_rays,
+                           int32_t* counts, float* stage_ts, float* stage_deltas,
+                           const int32_t* list, const int32_t* count, void* stream);
+int rn_gate_select_bw(const float* gate, const uint8_t* live, const float* dL_dgate_used,
+                      int64_t n_rays, int32_t n_models, int32_t renormalize, float* dL_dgate,
+                      void* stream);
+int rn_nerf_loss_routed(const float* rgb, const float* target_rgb, const float* opacity,
+                        const float* depth, const float* gate_used, const uint8_t* live,
+                        const float* importance, int64_t n_rays, int32_t n_models,
+                        float lambda_opacity, float lambda_cv, float lambda_dm, float* loss_out,
+                        float* dL_drgb, float* dL_dopacity, float* dL_ddepth, float* dL_dgate,
+                        void* stream);
+int rn_nerf_loss_routed_det(const float* rgb, const float* target_rgb, const float* opacity,
+                            const float* depth, const float* gate_used, const uint8_t* live,
+                            const float* importance, int64_t n_rays, int32_t n_models,
+                            float lambda_opacity, float lambda_cv, float lambda_dm,
+                            float* loss_out, float* part, float* dL_drgb, float* dL_dopacity,
+                            float* dL_ddepth, float* dL_dgate, void* stream);
+
 /* Exact integer accumulation of the merged backward's grid gradient
  * (optional; igrad_lo == NULL keeps fp32 atomics into grid_grad).  With
  * igrad_lo / igrad_carry (int32, one per grid_grad element, zero on entry) and

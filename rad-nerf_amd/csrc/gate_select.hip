@@ -167,9 +167,61 @@ __global__ void __launch_bounds__(GS_THREADS) k_gs_write(SelectArgs a) {
     }
 }
 
+// Routed training: the backward of k_gs_mark's gate_used with the selection
+// held constant (include/radnerf.h rn_gate_select_bw).  Lane per ray, the
+// row's gates, live bits and incoming gradients in registers; every load of
+// the row comes before its first store, so d_used and d_gate may be one buffer.
+__global__ void __launch_bounds__(GS_THREADS)
+k_gs_bw(const float* __restrict__ gate, const uint8_t* __restrict__ live, const float* d_used,
+        int64_t n, int K, int renorm, float* d_gate) {
+    const int64_t r = (int64_t)blockIdx.x * GS_THREADS + threadIdx.x;
+    if (r >= n) return;
+    float g[GS_MAX_K], d[GS_MAX_K];
+    uint32_t lv = 0;
+#pragma unroll
+    for (int i = 0; i < GS_MAX_K; ++i) {
+        const bool in = i < K;
+        g[i] = in ? gate[r * K + i] : 0.f;
+        d[i] = in ? d_used[r * K + i] : 0.f;
+        lv |= (in && live[r * K + i] != 0 ? 1u : 0u) << i;
+    }
+    // S as k_gs_mark forms it; D = sum over live j of d_j u_j, u_j = g_j / S
+    float S = 0.f, D = 0.f;
+#pragma unroll
+    for (int i = 0; i < GS_MAX_K; ++i)
+        if ((lv >> i) & 1u) S = S + g[i];
+    if (renorm) {
+#pragma unroll
+        for (int i = 0; i < GS_MAX_K; ++i)
+            if ((lv >> i) & 1u) D = D + d[i] * (g[i] / S);
+    }
+#pragma unroll
+    for (int i = 0; i < GS_MAX_K; ++i) {
+        if (i < K) {
+            float o = 0.f;
+            if ((lv >> i) & 1u) o = renorm ? (S == 0.f ? 0.f : (d[i] - D) / S) : d[i];
+            d_gate[r * K + i] = o;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int rn_gate_select_bw(const float* gate, const uint8_t* live, const float* dL_dgate_used,
+                      int64_t n_rays, int32_t n_models, int32_t renormalize, float* dL_dgate,
+                      void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_rays < (1ll << 31) && n_models >= 1 && n_models <= GS_MAX_K,
+                 "bad sizes (1 <= n_models <= 16)");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(gate && live && dL_dgate_used && dL_dgate, "null pointer");
+    k_gs_bw<<<nblk(n_rays, GS_THREADS), GS_THREADS, 0, (hipStream_t)stream>>>(
+        gate, live, dL_dgate_used, n_rays, n_models, renormalize != 0, dL_dgate);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
 
 int rn_gate_select(const float* gate, int64_t n_rays, int32_t n_models, float gate_min,
                    int32_t gate_topk, int32_t renormalize, uint8_t* live, float* gate_used,

@@ -235,6 +235,57 @@ k_ml_march_count(int n_rays, int K, const float* __restrict__ rays_o,
     if (rn_lane() == 0) counts[gid] = n;
 }
 
+// Routed training (rn_ml_march_count_list): the same march for the pairs of
+// rn_gate_select's lists only.  counts is zero on entry (the entry's memset),
+// so a pair no wave visits keeps count 0 and its staging slot is never written.
+// Wave w of the launch takes flat live pair w: the running sum of count[] gives
+// the sub-NeRF (K <= 16), list[k][w - sum] the ray, so the live work is dense at
+// the front of the grid and every wave past the total leaves at once.  The
+// per-pair statements are k_ml_march_count's, copied: a routine shared with
+// the dense kernel reorders two address computations in that kernel's code,
+// which is to stay the parent's instruction for instruction.
+constexpr int ML_LIST_MAX_K = 16;
+template <bool STAGE>
+__global__ void __launch_bounds__(256)
+k_ml_march_count_list(int n_rays, int K, const float* __restrict__ rays_o,
+                      const float* __restrict__ rays_d, const float* __restrict__ center,
+                      const float* __restrict__ half_size, float near_distance,
+                      const float* __restrict__ noise, const uint8_t* __restrict__ bitfields,
+                      int64_t bitfield_bytes, MarchCfg c, const int32_t* __restrict__ list,
+                      const int32_t* __restrict__ count, int32_t* __restrict__ counts,
+                      float* __restrict__ stage_ts, float* __restrict__ stage_dt) {
+    const int64_t w = (int64_t)blockIdx.x * (blockDim.x / RN_WAVE) + threadIdx.x / RN_WAVE;
+    int k = -1, j = 0;
+    int64_t before = 0;
+#pragma unroll
+    for (int i = 0; i < ML_LIST_MAX_K; ++i) {
+        // a count outside [0, n_rays] is clamped: no read past a model's list
+        const int ci = i < K ? min(max(count[i], 0), n_rays) : 0;
+        if (k < 0 && w < before + ci) { k = i; j = (int)(w - before); }
+        before += ci;
+    }
+    if (k < 0) return;
+    const int r = list[(int64_t)k * n_rays + j];
+    if (r < 0 || r >= n_rays) return;
+    const int gid = k * n_rays + r;
+    const float ox = rays_o[3 * r], oy = rays_o[3 * r + 1], oz = rays_o[3 * r + 2];
+    const float dx = rays_d[3 * r], dy = rays_d[3 * r + 1], dz = rays_d[3 * r + 2];
+    float t1, t2;
+    aabb(ox, oy, oz, dx, dy, dz, center, half_size, t1, t2);
+    if (!(t2 > 0)) { t1 = -1.0f; t2 = -1.0f; }              // intersection.cu:48
+    else { t1 = fmaxf(t1, 0.0f); if (t1 < near_distance) t1 = near_distance; }
+    t1 = perturbed_t1(t1, noise[gid], c);
+    int n;
+    if (STAGE)
+        n = march_ray_wave<true>(ox, oy, oz, dx, dy, dz, t1, t2, c.max_samples,
+                                 gid * c.max_samples, bitfields + (size_t)k * bitfield_bytes, c,
+                                 StageSink{stage_ts, stage_dt});
+    else
+        n = march_ray_wave<false>(ox, oy, oz, dx, dy, dz, t1, t2, c.max_samples, 0,
+                                  bitfields + (size_t)k * bitfield_bytes, c, NoSink{});
+    if (rn_lane() == 0) counts[gid] = n;
+}
+
 // staged samples -> compact model-major layout at the scanned offsets
 __global__ void __launch_bounds__(256)
 k_ml_compact(int n_rays, int K, int max_samples, const int32_t* __restrict__ counts,
@@ -589,6 +640,39 @@ int rn_ml_march_count(const float* rays_o, const float* rays_d, const float* cen
         k_ml_march_count<false><<<nblk(n_rays * n_models, 4), 256, 0, (hipStream_t)stream>>>(
             (int)n_rays, n_models, rays_o, rays_d, center, half_size, near_distance, noise,
             density_bitfields, bitfield_bytes, c, counts, nullptr, nullptr);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_ml_march_count_list(const float* rays_o, const float* rays_d, const float* center,
+                           const float* half_size, float near_distance, const float* noise,
+                           const uint8_t* density_bitfields, int64_t bitfield_bytes,
+                           int32_t n_models, int32_t cascades, float scale, float exp_step_factor,
+                           int32_t grid_size, int32_t max_samples, int64_t n_rays,
+                           int32_t* counts, float* stage_ts, float* stage_deltas,
+                           const int32_t* list, const int32_t* count, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_models >= 1 && n_models <= ML_LIST_MAX_K && cascades >= 1 &&
+                 grid_size >= 1 && max_samples >= 1, "bad sizes (1 <= n_models <= 16)");
+    RN_CHECK_ARG((stage_ts == nullptr) == (stage_deltas == nullptr), "stage_ts/stage_deltas: both or neither");
+    RN_CHECK_ARG(n_rays * n_models * (int64_t)max_samples < (int64_t)1 << 31, "staging too large");
+    RN_CHECK_ARG(bitfield_bytes >= (int64_t)cascades * grid_size * grid_size * grid_size / 8,
+                 "bitfield too small");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(rays_o && rays_d && center && half_size && noise && density_bitfields && counts &&
+                 list && count, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    RN_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * n_rays * n_models, st),
+                 "counts memset");
+    MarchCfg c = make_cfg(cascades, grid_size, max_samples, scale, scale, exp_step_factor);
+    // one wave per possible pair: the live ones are the first sum(count) waves
+    if (stage_ts)
+        k_ml_march_count_list<true><<<nblk(n_rays * n_models, 4), 256, 0, st>>>(
+            (int)n_rays, n_models, rays_o, rays_d, center, half_size, near_distance, noise,
+            density_bitfields, bitfield_bytes, c, list, count, counts, stage_ts, stage_deltas);
+    else
+        k_ml_march_count_list<false><<<nblk(n_rays * n_models, 4), 256, 0, st>>>(
+            (int)n_rays, n_models, rays_o, rays_d, center, half_size, near_distance, noise,
+            density_bitfields, bitfield_bytes, c, list, count, counts, nullptr, nullptr);
     RN_CHECK_LAUNCH();
     return 0;
 }

@@ -23,14 +23,21 @@ namespace {
 // [gridDim.x][4] instead -- block b stores its three sums into row b (no
 // atomics; block 0 keeps the cv^2 term in [0][2]) and k_loss_sum adds the rows
 // in block order.  The per-ray part and the seeds are the same code.
-template <bool DET>
-__global__ void __launch_bounds__(256)
-k_nerf_loss(int64_t B, int K, const float* __restrict__ rgb, const float* __restrict__ target,
-            const float* __restrict__ opacity, const float* __restrict__ depth,
-            const float* __restrict__ gate, const float* __restrict__ importance,
-            float lambda_opacity, float lambda_cv, float lambda_dm, float* __restrict__ loss_out,
-            float* __restrict__ d_rgb, float* __restrict__ d_opacity, float* __restrict__ d_depth,
-            float* __restrict__ d_gate) {
+// ROUTED (routed training, rn_nerf_loss_routed / _det): `gate` is gate_used
+// (exactly 0 on a dead pair, whose depth is 0 too) and live [B][K] marks the
+// pairs that were marched; a dead pair adds nothing to the depth-mutual sum and
+// gets d_depth = 0.  The divisor stays B K, so with every pair live the results
+// are the dense ones bit for bit.  importance is still the full softmax gate's
+// column sums and d_gate the seed on that gate.
+template <bool DET, bool ROUTED>
+__device__ __forceinline__ void
+nerf_loss_body(int64_t B, int K, const float* __restrict__ rgb, const float* __restrict__ target,
+               const float* __restrict__ opacity, const float* __restrict__ depth,
+               const float* __restrict__ gate, const uint8_t* __restrict__ live,
+               const float* __restrict__ importance, float lambda_opacity, float lambda_cv,
+               float lambda_dm, float* __restrict__ loss_out, float* __restrict__ d_rgb,
+               float* __restrict__ d_opacity, float* __restrict__ d_depth,
+               float* __restrict__ d_gate) {
     __shared__ float red[4][RN_WAVE];
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = r < B;
@@ -67,6 +74,7 @@ k_nerf_loss(int64_t B, int K, const float* __restrict__ rgb, const float* __rest
             const float s = 2.0f * lambda_dm / ((float)B * K);
             for (int k = 0; k < K; ++k) {
                 const float e = depth[r * K + k] - mean_d;
+                if (ROUTED && live[r * K + k] == 0) { d_depth[r * K + k] = 0.f; continue; }
                 l_dm += lambda_dm * e * e;
                 d_depth[r * K + k] = s * e;
             }
@@ -102,6 +110,35 @@ k_nerf_loss(int64_t B, int K, const float* __restrict__ rgb, const float* __rest
         else atomicAdd(&loss_out[q], x);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && use_cv) loss_out[2] = lambda_cv * var / den;
+}
+
+template <bool DET>
+__global__ void __launch_bounds__(256)
+k_nerf_loss(int64_t B, int K, const float* __restrict__ rgb, const float* __restrict__ target,
+            const float* __restrict__ opacity, const float* __restrict__ depth,
+            const float* __restrict__ gate, const float* __restrict__ importance,
+            float lambda_opacity, float lambda_cv, float lambda_dm, float* __restrict__ loss_out,
+            float* __restrict__ d_rgb, float* __restrict__ d_opacity, float* __restrict__ d_depth,
+            float* __restrict__ d_gate) {
+    nerf_loss_body<DET, false>(B, K, rgb, target, opacity, depth, gate, nullptr, importance,
+                               lambda_opacity, lambda_cv, lambda_dm, loss_out, d_rgb, d_opacity,
+                               d_depth, d_gate);
+}
+
+// a kernel of its own, so that the dense one keeps its code
+template <bool DET>
+__global__ void __launch_bounds__(256)
+k_nerf_loss_routed(int64_t B, int K, const float* __restrict__ rgb,
+                   const float* __restrict__ target, const float* __restrict__ opacity,
+                   const float* __restrict__ depth, const float* __restrict__ gate_used,
+                   const uint8_t* __restrict__ live, const float* __restrict__ importance,
+                   float lambda_opacity, float lambda_cv, float lambda_dm,
+                   float* __restrict__ loss_out, float* __restrict__ d_rgb,
+                   float* __restrict__ d_opacity, float* __restrict__ d_depth,
+                   float* __restrict__ d_gate) {
+    nerf_loss_body<DET, true>(B, K, rgb, target, opacity, depth, gate_used, live, importance,
+                              lambda_opacity, lambda_cv, lambda_dm, loss_out, d_rgb, d_opacity,
+                              d_depth, d_gate);
 }
 
 // deterministic mode: the blocks' partial sums of k_nerf_loss<true> in block
@@ -336,6 +373,46 @@ int rn_nerf_loss_det(const float* rgb, const float* target_rgb, const float* opa
     k_nerf_loss<true><<<nb, 256, 0, (hipStream_t)stream>>>(
         n_rays, n_models, rgb, target_rgb, opacity, depth, gate, importance, lambda_opacity,
         lambda_cv, lambda_dm, part, dL_drgb, dL_dopacity, dL_ddepth, dL_dgate);
+    RN_CHECK_LAUNCH();
+    k_loss_sum<<<1, 64, 0, (hipStream_t)stream>>>(part, nb, use_cv, loss_out);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_nerf_loss_routed(const float* rgb, const float* target_rgb, const float* opacity,
+                        const float* depth, const float* gate_used, const uint8_t* live,
+                        const float* importance, int64_t n_rays, int32_t n_models,
+                        float lambda_opacity, float lambda_cv, float lambda_dm, float* loss_out,
+                        float* dL_drgb, float* dL_dopacity, float* dL_ddepth, float* dL_dgate,
+                        void* stream) {
+    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1, "bad sizes");
+    RN_CHECK_ARG(rgb && target_rgb && opacity && depth && gate_used && live && importance &&
+                 loss_out && dL_drgb && dL_dopacity && dL_ddepth && dL_dgate, "null pointer");
+    RN_CHECK_HIP(hipMemsetAsync(loss_out, 0, 4 * sizeof(float), (hipStream_t)stream),
+                 "loss memset");
+    k_nerf_loss_routed<false><<<nblk(n_rays, 256), 256, 0, (hipStream_t)stream>>>(
+        n_rays, n_models, rgb, target_rgb, opacity, depth, gate_used, live, importance,
+        lambda_opacity, lambda_cv, lambda_dm, loss_out, dL_drgb, dL_dopacity, dL_ddepth, dL_dgate);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_nerf_loss_routed_det(const float* rgb, const float* target_rgb, const float* opacity,
+                            const float* depth, const float* gate_used, const uint8_t* live,
+                            const float* importance, int64_t n_rays, int32_t n_models,
+                            float lambda_opacity, float lambda_cv, float lambda_dm,
+                            float* loss_out, float* part, float* dL_drgb, float* dL_dopacity,
+                            float* dL_ddepth, float* dL_dgate, void* stream) {
+    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1, "bad sizes");
+    RN_CHECK_ARG(rgb && target_rgb && opacity && depth && gate_used && live && importance &&
+                 loss_out && part && dL_drgb && dL_dopacity && dL_ddepth && dL_dgate,
+                 "null pointer");
+    RN_CHECK_ARG(nblk(n_rays, 256) <= 0x7fffffff / 4, "too many rays");
+    const int nb = nblk(n_rays, 256);
+    const int use_cv = n_models > 1 && lambda_cv > 0.f;
+    k_nerf_loss_routed<true><<<nb, 256, 0, (hipStream_t)stream>>>(
+        n_rays, n_models, rgb, target_rgb, opacity, depth, gate_used, live, importance,
+        lambda_opacity, lambda_cv, lambda_dm, part, dL_drgb, dL_dopacity, dL_ddepth, dL_dgate);
     RN_CHECK_LAUNCH();
     k_loss_sum<<<1, 64, 0, (hipStream_t)stream>>>(part, nb, use_cv, loss_out);
     RN_CHECK_LAUNCH();

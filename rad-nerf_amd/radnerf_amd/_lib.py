@@ -85,6 +85,13 @@ SIGNATURES = {
     "rn_gate_select": [P, I64, I32, F32, I32, I32, P, P, P, P, P, P, P, P, P, P],
     "rn_render_test_list": [P, P, P, I64, I32, P, I64, I32, F32, F32, I32, I32, P, P, P, P, P, P,
                             P, P, F32, P, P, P, P, P, P, I32, P],
+    # routed training (FusedMLRenderer.forward(gate_topk=, gate_min=, renormalize=))
+    "rn_ml_march_count_list": [P, P, P, P, F32, P, P, I64, I32, I32, F32, F32, I32, I32, I64, P,
+                               P, P, P, P, P],
+    "rn_gate_select_bw": [P, P, P, I64, I32, I32, P, P],
+    "rn_nerf_loss_routed": [P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P, P, P, P],
+    "rn_nerf_loss_routed_det": [P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P, P, P, P,
+                                P],
     "rn_seed_scale": [P, P, I32, P, P, P, P, P, P],
     "rn_igrad_to_f32": [I64, P, P, P, P, P],
     "rn_field_fwd_merged": [P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P, P, P, P, P, P, P,

@@ -8,6 +8,14 @@ chain of HIP launches with no host synchronisation:
             -> ml_combine_fw
   backward: ml_combine_bw -> ml_composite_bw -> field_bwd -> gate_bwd
 
+Routed training (opt-in: gate_topk / gate_min / renormalize, DESIGN.md §4
+"Routed training") marches and differentiates the gate's live pairs only:
+
+  forward : gate_fwd -> gate_select (side stream) -> ml_march_count_list
+            -> ... the same chain, the combine weighted by gate_used
+  backward: ml_combine_bw -> gate_select_bw (+ the seed on the softmax gate)
+            -> the same chain, the composite backward weighted by gate_used
+
 Sample buffers are sized for the worst case (B*K*max_samples, + alignment),
 so sample counts never have to be read back; every kernel consumes the
 device-side counts.  Outputs equal the unfused drop-in path (rendering.py)
@@ -18,7 +26,8 @@ import collections
 import torch
 
 from . import layout as LY
-from ._lib import lib
+from . import sparse_gate
+from ._lib import GATE_SELECT_WORK_BYTES, lib
 from .networks import field_ptrs, model_bitfields
 
 MAX_SAMPLES = 1024
@@ -55,6 +64,22 @@ def _stream(dev):
 
 # per (device, stream): forward scratch shared by every workspace (level_buffers)
 _LEVEL_SCRATCH = {}
+
+
+def route_params(fn, G, gate_topk=None, gate_min=0.0, renormalize=False, always=False):
+    """The routing of a training step over G gated sub-NeRFs from its three
+    arguments (sparse_gate's rule): None for the dense chain -- one sub-NeRF,
+    or every pair kept (gate_topk None or G, gate_min 0) without
+    renormalisation and `always` off -- else (gate_topk, gate_min,
+    renormalize), checked.  ValueError naming the argument and its value;
+    touches no library."""
+    if G == 1:              # nothing to route: the arguments are accepted and ignored
+        return None
+    tau, k = sparse_gate.check_params(fn, G, gate_min, gate_topk)
+    renorm = bool(renormalize)
+    if sparse_gate.is_dense(G, tau, k) and not renorm and not always:
+        return None
+    return k, tau, renorm
 
 
 class Workspace:
@@ -103,6 +128,22 @@ class Workspace:
         self.dw_part = self.gate_part = None
         self.gate_dx = self.dxyz = self.ddir = self.drays_o = self.drays_d = None
         self.generation = 0         # forwards run through this workspace (_MLRenderFn)
+        self._route = None          # routed steps only (route_buffers)
+
+    def route_buffers(self):
+        """rn_gate_select's outputs for a routed step, allocated by the first
+        one: live / gate_used (B, K), list (K, B), count (K,) and the
+        selection's scratch.  They belong to the workspace generation: the
+        backward of a routed forward reads live and gate_used from here."""
+        if self._route is None:
+            B, K, dev = self.B, self.K, self.device
+            self._route = dict(
+                live=torch.empty(B, K, device=dev, dtype=torch.uint8),
+                gate_used=torch.empty(B, K, device=dev, dtype=torch.float32),
+                list=torch.empty(K, B, device=dev, dtype=torch.int32),
+                count=torch.zeros(K, device=dev, dtype=torch.int32),
+                work=torch.empty(GATE_SELECT_WORK_BYTES, device=dev, dtype=torch.uint8))
+        return self._route
 
     @property
     def dist_k(self):
@@ -413,6 +454,15 @@ class FusedMLRenderer:
         # level forward's input, the gate's side stream, fx_f32_levels as a tensor
         self._plan_key = self._side_stream = None
         self._prep_ready = self._dist_forward = False
+        # measurement and tests only (tools/routed_step.py's all-live overhead
+        # leg, the all-live identity test): run the routed launches (selection,
+        # list march, routing backward) even when the arguments keep every pair
+        # live; the product leaves it off, and such arguments take the dense
+        # chain, launch for launch
+        self._route_always = False
+        # the last forward's routing: None (dense) or (gate_topk, gate_min,
+        # renormalize) as checked; the backward follows it
+        self._routed = None
         self._f32_idx = (None, None)
 
     _NO_DET = ("FusedMLRenderer(deterministic=True) needs the merged backward (1 to 8 sub-NeRFs, "
@@ -510,14 +560,30 @@ class FusedMLRenderer:
         return self._bf
 
     # ------------------------------------------------------------------ forward
+    def route_params(self, gate_topk=None, gate_min=0.0, renormalize=False):
+        """The routing of a step from its three arguments: None for the dense
+        chain (one sub-NeRF, or every pair kept without renormalisation and
+        _route_always off), else (gate_topk, gate_min, renormalize) checked.
+        ValueError naming the argument and its value; no launch."""
+        return route_params("FusedMLRenderer", self.gate.out_dim, gate_topk, gate_min,
+                            renormalize, self._route_always)
+
     def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4,
-                exp_step_factor=0.0, distortion=False):
+                exp_step_factor=0.0, distortion=False, gate_topk=None, gate_min=0.0,
+                renormalize=False):
         """distortion: the composite also writes each segment's Mip-NeRF 360
         distortion loss into ws.dist_k (rn_ml_composite_dist_fw; every other
-        output is the plain kernel's), for backward(dL_ddist=...)."""
+        output is the plain kernel's), for backward(dL_ddist=...).
+        gate_topk / gate_min / renormalize: routed training -- rn_gate_select's
+        rule (sparse_gate) decides which (ray, sub-NeRF) pairs are live; only
+        those are marched (a dead pair has no samples), and the render is
+        combined with gate_used (ws.route_buffers()), which backward() then
+        differentiates.  The returned gate stays the softmax.  The defaults
+        keep every pair and run the dense chain."""
         m, g, w, L = self.model, self.gate, self.ws, lib()
         B, K, G = rays_o.shape[0], m.size, g.out_dim     # K rendered here, G gated
         assert B == w.B and noise.shape == (K, B)
+        routed = self._routed = self.route_params(gate_topk, gate_min, renormalize)
         st = _stream(rays_o.device)
         out_gate = torch.empty(B, G, device=rays_o.device)
         imp = torch.zeros(G, device=rays_o.device)
@@ -540,6 +606,16 @@ class FusedMLRenderer:
                 # gate.sum(0) as an ordered sum instead of one atomic per wave
                 self._ev("gate_colsum", L.colsum_ordered, out_gate.data_ptr(), B, G,
                          imp.data_ptr(), side.cuda_stream, stream=side)
+        rt = None
+        if routed is not None:
+            # the selection follows the gate on its stream; the march needs the lists
+            rt = w.route_buffers()
+            self._ev("gate_select", L.gate_select, out_gate.data_ptr(), B, G, routed[1],
+                     routed[0], int(routed[2]), rt["live"].data_ptr(),
+                     rt["gate_used"].data_ptr(), rt["list"].data_ptr(), rt["count"].data_ptr(),
+                     None, None, None, None, rt["work"].data_ptr(), side.cuda_stream,
+                     stream=side)
+            main.wait_stream(side)
         bits = self.bitfields()
         march = (rays_o.data_ptr(), rays_d.data_ptr(), m.center.data_ptr(),
                  m.half_size.data_ptr(), NEAR_DISTANCE, noise.data_ptr(), bits.data_ptr(),
@@ -547,8 +623,13 @@ class FusedMLRenderer:
                  m.grid_size, MAX_SAMPLES, B)
         # single pass: march once into per-(model, ray) staging slots, scan the
         # counts, compact (the two-pass form re-marches every ray instead)
-        self._ev("march", L.ml_march_count, *march, w.counts.data_ptr(),
-                 w.stage_ts.data_ptr(), w.stage_dt.data_ptr(), st)
+        if rt is None:
+            self._ev("march", L.ml_march_count, *march, w.counts.data_ptr(),
+                     w.stage_ts.data_ptr(), w.stage_dt.data_ptr(), st)
+        else:
+            self._ev("march", L.ml_march_count_list, *march, w.counts.data_ptr(),
+                     w.stage_ts.data_ptr(), w.stage_dt.data_ptr(), rt["list"].data_ptr(),
+                     rt["count"].data_ptr(), st)
         self._ev("scan", L.scan_segments, w.counts.data_ptr(), K, B, SEG_ALIGN,
                  w.offsets.data_ptr(), w.seg_base.data_ptr(), w.seg_count.data_ptr(),
                  w.meta.data_ptr(), st)
@@ -577,7 +658,8 @@ class FusedMLRenderer:
         main.wait_stream(side)            # gate output joins here
         out_gate.record_stream(side)
         imp.record_stream(side)
-        self._ev("combine_fw", L.ml_combine_fw, out_gate.data_ptr(), ok.data_ptr(), dk.data_ptr(),
+        weights = out_gate if rt is None else rt["gate_used"]
+        self._ev("combine_fw", L.ml_combine_fw, weights.data_ptr(), ok.data_ptr(), dk.data_ptr(),
                         rk.data_ptr(), bg.data_ptr(), B, G, rgb.data_ptr(),
                         opacity.data_ptr(), depth.data_ptr(), st)
         return rgb, opacity, depth, out_gate, imp
@@ -878,6 +960,14 @@ class FusedMLRenderer:
         dgate = self._dgate(B, G)
         self._ev("combine_bw", L.ml_combine_bw, dL_drgb.data_ptr(), dL_dopacity.data_ptr(),
                  ok.data_ptr(), rk.data_ptr(), bg.data_ptr(), B, G, dgate.data_ptr(), st)
+        if self._routed is not None:
+            # through gate_used = select(gate), the selection held constant:
+            # dead pairs 0 (combine_bw leaves bg . dL_drgb there), live pairs
+            # the renormalisation's gradient; `gate` is the softmax
+            rt = w.route_buffers()
+            self._ev("gate_select_bw", L.gate_select_bw, gate.data_ptr(), rt["live"].data_ptr(),
+                     dgate.data_ptr(), B, G, int(self._routed[2]), dgate.data_ptr(), st)
+            gate = rt["gate_used"]      # the composite backward's weights
         if dL_dgate_ext is not None:
             dgate.add_(dL_dgate_ext)
         side = self._side(dev)
@@ -995,7 +1085,8 @@ class FusedMLRenderer:
     def train_step(self, rays_o, rays_d, gate_in2, target_rgb, noise, bg, lambda_opacity=1e-3,
                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0, T_threshold=1e-4,
                    exp_step_factor=0.0, grid_grad=None, mlp_grad=None, gate_grad=None,
-                   lambda_distortion=0.0, input_grad=False):
+                   lambda_distortion=0.0, input_grad=False, gate_topk=None, gate_min=0.0,
+                   renormalize=False):
         """render -> NeRFLoss -> backward of train_ml.py:179-192 as one launch
         chain: the fused loss kernel writes the backward seeds directly.
         Returns ({term: mean}, (grid_grad, mlp_grad, gate_grad)); gradients are
@@ -1009,19 +1100,30 @@ class FusedMLRenderer:
         (B, 3) each: the first sums the march's and the gate's share, the last
         is the gradient of the gate's second input alone (add it to dL/drays_d
         when that input is rays_d).  The last two are views of the workspace:
-        use them before the next backward."""
+        use them before the next backward.
+        gate_topk / gate_min / renormalize: a routed step (forward()); the
+        loss's depth-mutual term then covers the live pairs only, its cv^2
+        term still the softmax gate's importance, and last_forward also holds
+        gate_used, live and route_count ((K,) int32 on the device: the rays
+        routed to each sub-NeRF)."""
         from .losses import fused_nerf_loss
         dist = lambda_distortion > 0
         rgb, opacity, depth, gate, imp = self.forward(rays_o, rays_d, gate_in2, noise, bg,
-                                                      T_threshold, exp_step_factor, dist)
+                                                      T_threshold, exp_step_factor, dist,
+                                                      gate_topk, gate_min, renormalize)
         # the step's render, for callers that log it (train_step returns the
         # loss terms and the gradients only)
         self.last_forward = {"rgb": rgb, "opacity": opacity, "depth": depth, "gate": gate,
                              "importance": imp}
+        rt = None if self._routed is None else self.ws.route_buffers()
+        if rt is not None:
+            self.last_forward.update(gate_used=rt["gate_used"], live=rt["live"],
+                                     route_count=rt["count"])
         terms, (d_rgb, d_op, d_depth, d_gate) = fused_nerf_loss(
-            rgb, target_rgb, opacity, depth, gate, imp, lambda_opacity, lambda_cv_importance,
-            lambda_depth_mutual, lambda_distortion, self.ws.dist_k if dist else None,
-            deterministic=self.deterministic)
+            rgb, target_rgb, opacity, depth, gate if rt is None else rt["gate_used"], imp,
+            lambda_opacity, lambda_cv_importance, lambda_depth_mutual, lambda_distortion,
+            self.ws.dist_k if dist else None, deterministic=self.deterministic,
+            live=None if rt is None else rt["live"])
         d_dist = float(lambda_distortion) / rays_o.shape[0] if dist else None
         if not input_grad:
             grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
@@ -1040,9 +1142,9 @@ class FusedMLRenderer:
 class _MLRenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid_params, mlp_params, gate_params, renderer, rays_o, rays_d, gate_in2,
-                noise, bg, T_threshold, esf, distortion=False):
+                noise, bg, T_threshold, esf, distortion=False, route=(None, 0.0, False)):
         rgb, opacity, depth, gate, imp = renderer.forward(rays_o, rays_d, gate_in2, noise, bg,
-                                                          T_threshold, esf, distortion)
+                                                          T_threshold, esf, distortion, *route)
         # the backward reads this step's samples from the renderer's workspace:
         # stamp it, so a second forward through the same workspace before this
         # backward is caught instead of silently differentiating the wrong step
@@ -1087,7 +1189,7 @@ class _MLRenderFn(torch.autograd.Function):
             do = w.drays_o + w.gate_dx[:, 0:3] if need_o else None
             dd = w.drays_d.clone() if need_d else None
             d2 = w.gate_dx[:, 3:6].contiguous() if need_2 else None
-        return gg, mg, ag, None, do, dd, d2, None, None, None, None, None
+        return gg, mg, ag, None, do, dd, d2, None, None, None, None, None, None
 
 
 class _GradNotSupported(torch.autograd.Function):
@@ -1165,7 +1267,15 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     and differentiated inside the composite kernels.  NeRFLoss(lambda_distortion
     > 0) reads it.  deterministic=True renders through a
     FusedMLRenderer(deterministic=True), a renderer and workspace of its own:
-    the backward's gradients are then bitwise reproducible."""
+    the backward's gradients are then bitwise reproducible.
+    gate_topk= / gate_min= / renormalize=: routed training (FusedMLRenderer.
+    forward).  "gating_code" and "gating_importance" stay the softmax gate and
+    its column sums, differentiable; "gating_used" (B, K) and "gating_live"
+    (B, K) bool are added, values only.  Column i of "depth" is 0 for a dead
+    pair and independent_rgbs[i] is the background there."""
+    route = (kwargs.get("gate_topk"), kwargs.get("gate_min", 0.0),
+             bool(kwargs.get("renormalize", False)))
+    route_params("ml_render", gating_net.out_dim, *route)     # ValueError before any launch
     rays_o, rays_d = rays_o.float().contiguous(), rays_d.float().contiguous()
     second = imgs_d.float().contiguous() if gating_net.type == "image" else rays_d
     B, K, dev = rays_o.shape[0], model.size, rays_o.device
@@ -1182,10 +1292,13 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     r = get_renderer(model, gating_net, B, grad=torch.is_grad_enabled(),
                      deterministic=bool(kwargs.get("deterministic", False)))
     distortion = bool(kwargs.get("distortion", False))
+    routed = r.route_params(*route) is not None
     fn_args = (model.xyz_encoder.params, model.mlp_params, gating_net.params, r, rays_o, rays_d,
                second, noise.contiguous(), bg, float(kwargs.get("T_threshold", 1e-4)), esf)
     if distortion:
-        rgb, opacity, depth, gate, dist = _MLRenderFn.apply(*fn_args, True)
+        rgb, opacity, depth, gate, dist = _MLRenderFn.apply(*fn_args, True, route)
+    elif routed:
+        rgb, opacity, depth, gate = _MLRenderFn.apply(*fn_args, False, route)
     else:
         rgb, opacity, depth, gate = _MLRenderFn.apply(*fn_args)
     w = r.ws
@@ -1199,4 +1312,8 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
            "gating_code": gate, "gating_importance": gate.sum(0)}
     if distortion:
         out["distortion"] = dist
+    if routed:
+        rt = w.route_buffers()
+        out["gating_used"] = rt["gate_used"].clone()
+        out["gating_live"] = rt["live"].bool()
     return out

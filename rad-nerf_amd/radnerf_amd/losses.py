@@ -80,7 +80,7 @@ class NeRFLoss(nn.Module):
 
 def fused_nerf_loss(rgb, target_rgb, opacity, depth, gate, importance, lambda_opacity=1e-3,
                     lambda_cv_importance=0.0, lambda_depth_mutual=0.0, lambda_distortion=0.0,
-                    dist_k=None, deterministic=False):
+                    dist_k=None, deterministic=False, live=None):
     """Returns ({term: mean (0-d tensor)}, (dL_drgb, dL_dopacity, dL_ddepth, dL_dgate))
     for loss = sum of the term means.  All inputs fp32 CUDA, contiguous.
     lambda_distortion > 0 with dist_k (the [K][B] per-segment distortion loss
@@ -89,7 +89,11 @@ def fused_nerf_loss(rgb, target_rgb, opacity, depth, gate, importance, lambda_op
     goes to FusedMLRenderer.backward(dL_ddist=...).
     deterministic=True sums the per-ray terms as per-block partials added in
     block order (rn_nerf_loss_det) instead of one fp32 atomic per block: the
-    same seeds bit for bit, and terms that do not vary from run to run."""
+    same seeds bit for bit, and terms that do not vary from run to run.
+    live ((B, K) uint8, a routed step): `gate` is then gate_used, a dead
+    pair adds nothing to the depth-mutual term and gets dL_ddepth = 0 (the
+    divisor stays B K); `importance` is still the softmax gate's column sums
+    and dL_dgate the seed on that gate (rn_nerf_loss_routed / _det)."""
     B, K = gate.shape
     dev = rgb.device
     f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
@@ -98,16 +102,21 @@ def fused_nerf_loss(rgb, target_rgb, opacity, depth, gate, importance, lambda_op
     c = lambda t: t.float().contiguous()
     rgb, target_rgb, opacity, depth, gate, importance = map(
         c, (rgb, target_rgb, opacity, depth, gate, importance))
+    if live is not None:
+        assert live.shape == (B, K) and live.dtype == torch.uint8 and live.is_contiguous()
     head = (rgb.data_ptr(), target_rgb.data_ptr(), opacity.data_ptr(), depth.data_ptr(),
-            gate.data_ptr(), importance.data_ptr(), B, K, float(lambda_opacity),
+            gate.data_ptr(), *(() if live is None else (live.data_ptr(),)),
+            importance.data_ptr(), B, K, float(lambda_opacity),
             float(lambda_cv_importance), float(lambda_depth_mutual), out.data_ptr())
     seeds = (d_rgb.data_ptr(), d_op.data_ptr(), d_depth.data_ptr(), d_gate.data_ptr(),
              torch.cuda.current_stream(dev).cuda_stream)
+    L = lib()
     if deterministic:
         part = f((B + 255) // 256, 4)
-        lib().nerf_loss_det(*head, part.data_ptr(), *seeds)
+        (L.nerf_loss_det if live is None else L.nerf_loss_routed_det)(
+            *head, part.data_ptr(), *seeds)
     else:
-        lib().nerf_loss(*head, *seeds)
+        (L.nerf_loss if live is None else L.nerf_loss_routed)(*head, *seeds)
     terms = {"rgb": out[0] / (3 * B), "opacity": out[1] / B}
     if lambda_distortion > 0 and dist_k is not None:
         terms["distortion"] = lambda_distortion * dist_k.sum() / B

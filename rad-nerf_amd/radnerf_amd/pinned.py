@@ -26,7 +26,7 @@ grid is shared), as SURVEY.md §8(e) notes.
 import torch
 import torch.distributed as dist
 
-from .fused import FusedMLRenderer
+from .fused import FusedMLRenderer, route_params
 
 
 class ModelSlice:
@@ -105,10 +105,16 @@ class PinnedMLRenderer(FusedMLRenderer):
     _NO_DISTORTION = ("PinnedMLRenderer: the in-chain distortion loss is not supported in the "
                       "sub-NeRF-per-GPU layout; use the data-parallel renderer")
 
+    _NO_ROUTING = ("PinnedMLRenderer: routed training (gate_topk / gate_min / renormalize) is "
+                   "not supported in the sub-NeRF-per-GPU layout; use the data-parallel renderer")
+
     def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4, exp_step_factor=0.0,
-                distortion=False):
+                distortion=False, gate_topk=None, gate_min=0.0, renormalize=False):
         if distortion:
             raise NotImplementedError(self._NO_DISTORTION)
+        if route_params("PinnedMLRenderer", noise.shape[0], gate_topk, gate_min,
+                        renormalize) is not None:
+            raise NotImplementedError(self._NO_ROUTING)
         return super().forward(rays_o, rays_d, gate_in2, noise[self.k0:self.k1], bg, T_threshold,
                                exp_step_factor)
 

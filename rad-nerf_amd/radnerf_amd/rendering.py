@@ -296,11 +296,21 @@ def ml_render(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **kwargs)
     fused chain the composite kernels compute and differentiate it; with
     fused=False it is DistortionLoss.apply on the reference's per-sub-NeRF keys
     ws_i / deltas_i / ts_i / rays_a_i (losses.py:63-67), which are returned
-    too.  NeRFLoss(lambda_distortion > 0) works on either result."""
+    too.  NeRFLoss(lambda_distortion > 0) works on either result.
+    gate_topk= / gate_min= / renormalize= (fused training renders only, else
+    NotImplementedError): routed training, see fused.ml_render_fused -- adds
+    "gating_used" and "gating_live"."""
     fused = kwargs.pop("fused", True)
     if fused and not kwargs.get("test_time", False):
         from .fused import ml_render_fused
         return ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup, **kwargs)
+    from .fused import route_params
+    if route_params("ml_render", gating_net.out_dim, kwargs.pop("gate_topk", None),
+                    kwargs.pop("gate_min", 0.0), kwargs.pop("renormalize", False)) is not None:
+        raise NotImplementedError(
+            "ml_render: routed training (gate_topk / gate_min / renormalize) runs on the fused "
+            "training chain only; render with fused=True (ImageEvaluator.render_image is the "
+            "gate-sparse test-time render)")
     with torch.autocast("cuda"):
         rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
         second = imgs_d.contiguous() if gating_net.type == "image" else rays_d

@@ -89,13 +89,14 @@ logging back-ends.
 """
 import copy
 import math
+import numbers
 import os
 
 import torch
 
 from . import dist as rdist
 from . import train_state as TS
-from .fused import FusedMLRenderer
+from .fused import FusedMLRenderer, route_params
 from .optim import FusedAdam
 
 MAX_SAMPLES = 1024
@@ -118,14 +119,25 @@ class Trainer:
     val_save_dir = None
     # fit_resumable(ckpt_dir=...): write the checkpoints with save_state(background=True)
     ckpt_background = True
+    # routed training (Trainer(gate_topk=, gate_min=, renormalize=,
+    # route_from_step=)): the defaults keep every pair on every step
+    gate_topk, gate_min, renormalize, route_from_step = None, 0.0, False, 0
 
     def __init__(self, model, gating_net, n_rays, lr=1e-2, lambda_opacity=1e-3,
                  lambda_cv_importance=0.0, lambda_depth_mutual=0.0, exp_step_factor=None,
                  random_bg=False, update_interval=16, warmup_steps=256, seed=0,
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
                  optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None, intrinsics=None,
-                 cull_invisible=False, erode=False, deterministic=False):
-        """deterministic=True: the renderer is FusedMLRenderer(deterministic=
+                 cull_invisible=False, erode=False, deterministic=False, gate_topk=None,
+                 gate_min=0.0, renormalize=False, route_from_step=0):
+        """gate_topk / gate_min / renormalize: routed training (FusedMLRenderer.
+        forward; DESIGN.md §4 "Routed training") -- every step from global_step
+        route_from_step on marches and differentiates only the (ray, sub-NeRF)
+        pairs the gate keeps; the steps before it train dense, so the gate can
+        form before it is cut.  `routing` hands the same three arguments to
+        validate().  ValueError for gate_topk outside 1..K, gate_min outside
+        [0, 1) or route_from_step < 0, before anything is allocated.
+        deterministic=True: the renderer is FusedMLRenderer(deterministic=
         True) (ValueError above 8 sub-NeRFs).  With step_sampled / fit, whose
         batches are a hash of (seed, global_step, rank), every parameter, Adam
         moment, density grid, bitfield and loss term after any number of steps
@@ -165,6 +177,15 @@ class Trainer:
                 raise ValueError(f"Trainer: images are {images.n_images} x {images.n_pix} pixels "
                                  f"for {poses.shape[0]} poses and {directions.shape[0]} rows of "
                                  "directions")
+        # (one sub-NeRF: nothing to route, the arguments are accepted and ignored)
+        route_params("Trainer", gating_net.out_dim, gate_topk, gate_min, renormalize)
+        if isinstance(route_from_step, bool) or not isinstance(route_from_step, numbers.Integral) \
+                or route_from_step < 0:
+            raise ValueError(f"Trainer: route_from_step must be an int >= 0, got "
+                             f"{route_from_step!r}")
+        self.gate_topk = None if gate_topk is None else int(gate_topk)
+        self.gate_min, self.renormalize = float(gate_min), bool(renormalize)
+        self.route_from_step = int(route_from_step)
         # step_sampled()'s training set and its reused batch buffers
         self.images, self.last_batch = images, None
         self.n_rays, self.lr0 = int(n_rays), float(lr)
@@ -231,6 +252,18 @@ class Trainer:
         self.n_culled = None
         if cull_invisible:
             self.n_culled = model.mark_invisible_cells(intrinsics, self.poses, self.img_wh)
+
+    @property
+    def routing(self):
+        """The routing this trainer trains with, as validate()'s and
+        ImageEvaluator.render_image's keyword arguments: validate(poses,
+        images, **trainer.routing) renders what was trained."""
+        return {"gate_topk": self.gate_topk, "gate_min": self.gate_min,
+                "renormalize": self.renormalize}
+
+    def _route_now(self):
+        """this step's routing arguments: dense before route_from_step"""
+        return self.routing if self.global_step >= self.route_from_step else {}
 
     def _bg(self):
         """ml_rendering.py:192-198"""
@@ -309,12 +342,13 @@ class Trainer:
             terms, _ = self.renderer.train_step(rays_o, rays_d, second, target_rgb, noise,
                                                 bg, exp_step_factor=self.esf,
                                                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2],
-                                                **self.lambdas)
+                                                **self.lambdas, **self._route_now())
         else:
             from . import rays as R
             terms, _, (g_o, g_d, g_2) = self.renderer.train_step(
                 rays_o, rays_d, second, target_rgb, noise, bg, exp_step_factor=self.esf,
-                grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2], input_grad=True, **self.lambdas)
+                grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2], input_grad=True, **self.lambdas,
+                **self._route_now())
             # the gate's second input is rays_d ("ray") or imgs_d ("image")
             if self.gate.type == "image":
                 g_i = g_2.contiguous()
@@ -350,6 +384,18 @@ class Trainer:
                 "n_images": 0 if self.poses is None else int(self.poses.shape[0]),
                 "world_size": _world()}
 
+    def _dense_hyper(self):
+        """the routing fields of a trainer that keeps every pair"""
+        return {"gate_topk": int(self.gate.out_dim), "gate_min": 0.0, "renormalize": False,
+                "route_from_step": 0}
+
+    def _route_hyper(self):
+        """this trainer's (gate_topk None is all of them)"""
+        k = self.gate.out_dim if self.gate_topk is None else self.gate_topk
+        return {"gate_topk": int(k), "gate_min": float(self.gate_min),
+                "renormalize": bool(self.renormalize),
+                "route_from_step": int(self.route_from_step)}
+
     def _hyper(self):
         """What a state must match unless load_state(override=True)."""
         h = {"n_rays": int(self.n_rays), "seed": int(self.seed),
@@ -359,6 +405,12 @@ class Trainer:
              "random_bg": bool(self.random_bg), "erode": bool(self.erode),
              "deterministic": bool(self.deterministic)}
         h.update({k: float(v) for k, v in self.lambdas.items()})
+        # the routing joins the table when it is set: a dense trainer's state
+        # keeps the fields it had before routing existed, and a state without
+        # them loads as dense (_load fills them in)
+        route = self._route_hyper()
+        if route != self._dense_hyper():
+            h.update(route)
         for i, g in enumerate(self.opt.param_groups):
             h[f"adam.{i}.betas"] = [float(b) for b in g["betas"]]
             h[f"adam.{i}.eps"] = float(g["eps"])
@@ -423,7 +475,10 @@ class Trainer:
         self.wait_saves()
         if not verified:
             TS.verify(state, where)
-        TS.check_compatible(state, self._structure(), self._hyper(), override, where)
+        # a state without the routing fields was trained dense
+        dense = self._dense_hyper()
+        TS.check_compatible({**state, "hyper": {**dense, **state.get("hyper", {})}},
+                            self._structure(), {**dense, **self._hyper()}, override, where)
         m, dev = self.model, self.device
         copies, moments = [], []
 
