@@ -848,6 +848,83 @@ int rn_sample_batch(const void* images, int32_t image_dtype, int64_t n_images, i
                     float* imgs_d /*may be NULL*/, float* noise /*may be NULL*/,
                     float* bg /*may be NULL*/, void* stream);
 
+/* ---- error-guided pixel sampling ---------------------------------------------
+ * A tiled error map over the training set steers rn_sample_batch's picks to
+ * where the loss is, and each ray's seeds are divided by its sampling density,
+ * so the gradient stays an unbiased estimate of the uniform batch's.
+ * Geometry: images of W x H pixels (pixel index y W + x, as `directions`), a
+ * tile edge `tile` in 1..256, tw = ceil(W / tile), th = ceil(H / tile); cell
+ * c = (img th + ty) tw + tx, n_cells = n_images th tw < 2^24; edge cells are
+ * narrower or shorter: cw(tx) = min(tile, W - tx tile), ch(ty) likewise,
+ * n_px(c) = cw ch.  Per cell: emap fp32 (a fresh map is all 1.0), acc_sum
+ * uint64 and acc_cnt uint32 (filled between refreshes), w uint32, cdf uint64.
+ *
+ * rn_guided_weights: w[c] = clamp(rintf(emap[c] * 65536.0f), 1, 2^24) (a NaN
+ * clamps to 1), mass[c] = (uint64)w[c] n_px(c), cdf = the inclusive uint64
+ * prefix sum of mass in cell order; total = cdf[n_cells - 1] < 2^64.  Integer
+ * sums: any scan tree gives these bits.  Three launches on `stream` (block
+ * sums, their scan, the cells), no host synchronisation.  work:
+ * RN_GUIDED_WORK_BYTES of device scratch (8-byte aligned), not shared by
+ * calls in flight on different streams.
+ *
+ * rn_sample_batch_guided: rn_sample_batch's arguments, outputs and stream,
+ * plus cell_idx (n_rays) int32 and ray_weight (n_rays) fp32; n_pix == W H.
+ * Per ray i, with key, G, mix and unit as above:
+ *   z = mix(key + (i + 1) G)                          (rn_sample_batch's draw)
+ *   u = unit(mix((key ^ 0xa0761d6478bd642f) + (i + 1) G))
+ *   u < uniform_frac (an fp32 compare): the uniform branch, rn_sample_batch's
+ *     picks from z;
+ *   else: z2 = mix((key ^ 0xe7037ed1a0b428db) + (i + 1) G), t = mulhi64(z2,
+ *     total); c = the smallest cell with cdf[c] > t; j = (t - cdf[c - 1]) /
+ *     w[c] (cdf[-1] = 0; j < n_px(c)); the pixel is (y, x) = (ty tile + j /
+ *     cw, tx tile + j % cw).
+ *   cell_idx = the cell of the picked pixel, in either branch;
+ *   ray_weight = (float)(1.0 / ((double)f + (((1.0 - f) (double)w[cell])
+ *     (double)N_all) / (double)total)), f = (double)uniform_frac, N_all =
+ *     n_images n_pix, the operations doubles in that order: (1 / N_all) / p
+ *     for the mixture p = f / N_all + (1 - f) w / total, at most 1 / f.
+ * Targets, rays, jitter and background are rn_sample_batch's on these picks.
+ * The search runs in two levels (the images' last cdf entries, staged in LDS
+ * for up to 20480 images, then the image's cells) and finds the cell a plain
+ * binary search over cdf finds.  Status 1 also for tile outside 1..256, W H
+ * != n_pix, n_cells >= 2^24, uniform_frac outside [0, 1].
+ *
+ * rn_guided_epilogue: after the loss kernel, before the backward.  Per ray r:
+ * d = rgb[r] - target[r], e = (d0 d0 + d1 d1) + d2 d2 (fp32, no contraction);
+ * a finite e adds (uint64)min(rintf(e * 2^20), 2^24) to acc_sum[cell_idx[r]]
+ * and 1 to acc_cnt (integer atomics, no return value: order-free and exact;
+ * the lanes of a wave that share a cell are summed first and issue one pair),
+ * a non-finite e and a cell outside [0, n_cells) add nothing.  Then
+ * dL_drgb[r, :], dL_dopacity[r] and dL_ddepth[r, :] ((n_rays, n_models), may
+ * be NULL) are multiplied in place by ray_weight[r], one fp32 multiply each.
+ * acc_sum / acc_cnt may be NULL together (scale only, cell_idx is not read).
+ *
+ * rn_guided_refresh: for cells with acc_cnt > 0, mean = (float)(((double)
+ * acc_sum * 2^-20) / (double)acc_cnt) and emap = emap + alpha * (mean - emap)
+ * (fp32, no contraction); other cells keep their value; both accumulators are
+ * zeroed.  alpha in (0, 1].
+ * All four: plain and vector stores, no host synchronisation.                */
+#define RN_GUIDED_WORK_BYTES 131072
+int rn_guided_weights(const float* emap, int64_t n_images, int32_t W, int32_t H, int32_t tile,
+                      uint32_t* w, uint64_t* cdf, void* work, void* stream);
+int rn_sample_batch_guided(const void* images, int32_t image_dtype, int64_t n_images,
+                           int64_t n_pix, const float* directions, const float* poses,
+                           const float* dR, const float* dT, const float* mean_dir,
+                           uint64_t seed, int64_t step, int32_t rank, int64_t n_rays,
+                           int32_t n_models, int64_t* img_idxs, int64_t* pix_idxs,
+                           float* target_rgb, float* rays_o, float* rays_d,
+                           float* imgs_d /*may be NULL*/, float* noise /*may be NULL*/,
+                           float* bg /*may be NULL*/, int32_t W, int32_t H, int32_t tile,
+                           float uniform_frac, const uint32_t* w, const uint64_t* cdf,
+                           int32_t* cell_idx, float* ray_weight, void* stream);
+int rn_guided_epilogue(const float* rgb, const float* target_rgb, const int32_t* cell_idx,
+                       const float* ray_weight, int64_t n_rays, int32_t n_models,
+                       int64_t n_cells, uint64_t* acc_sum /*may be NULL*/,
+                       uint32_t* acc_cnt /*may be NULL*/, float* dL_drgb, float* dL_dopacity,
+                       float* dL_ddepth /*may be NULL*/, void* stream);
+int rn_guided_refresh(float* emap, uint64_t* acc_sum, uint32_t* acc_cnt, int64_t n_cells,
+                      float alpha, void* stream);
+
 /* ---- whole-image validation (train_ml.py:214-250) ---------------------------
  * rn_ml_combine_test: the test-time epilogue of ml_rendering.py:65-68,149-153
  * (background, gate-weighted combine) plus the gated depth of train_ml.py:243,

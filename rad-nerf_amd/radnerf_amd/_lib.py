@@ -114,6 +114,12 @@ SIGNATURES = {
     "rn_get_rays_pose_bw": [P, P, P, P, P, I64, I64, P, P, P, P, P, P, P],
     "rn_sample_batch": [P, I32, I64, I64, P, P, P, P, P, U64, I64, I32, I64, I32, P, P, P, P, P,
                         P, P, P, P],
+    # error-guided sampling (sampler.GuidedSampler, Trainer(guided=True))
+    "rn_guided_weights": [P, I64, I32, I32, I32, P, P, P, P],
+    "rn_sample_batch_guided": [P, I32, I64, I64, P, P, P, P, P, U64, I64, I32, I64, I32, P, P, P,
+                               P, P, P, P, P, I32, I32, I32, F32, P, P, P, P, P],
+    "rn_guided_epilogue": [P, P, P, P, I64, I32, I64, P, P, P, P, P, P],
+    "rn_guided_refresh": [P, P, P, I64, F32, P],
     "rn_ml_combine_test": [P, P, P, P, P, I64, I32, I64, P, P, P, P, P],
     "rn_image_sse": [P, P, I64, P, P, P],
     "rn_ssim": [P, P, I32, I32, I32, P, P, P, P],
@@ -134,6 +140,7 @@ SIGNATURES = {
 ABI_VERSION = 9
 METRICS_WORK_BYTES = 8192       # include/radnerf.h RN_METRICS_WORK_BYTES
 GATE_SELECT_WORK_BYTES = 65536  # include/radnerf.h RN_GATE_SELECT_WORK_BYTES
+GUIDED_WORK_BYTES = 131072      # include/radnerf.h RN_GUIDED_WORK_BYTES
 _lib = None
 
 _CODE = {P: "p", I32: "i", I64: "l", F32: "f", F64: "d", U64: "u"}

@@ -1086,7 +1086,7 @@ class FusedMLRenderer:
                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0, T_threshold=1e-4,
                    exp_step_factor=0.0, grid_grad=None, mlp_grad=None, gate_grad=None,
                    lambda_distortion=0.0, input_grad=False, gate_topk=None, gate_min=0.0,
-                   renormalize=False):
+                   renormalize=False, ray_weight=None, guided=None):
         """render -> NeRFLoss -> backward of train_ml.py:179-192 as one launch
         chain: the fused loss kernel writes the backward seeds directly.
         Returns ({term: mean}, (grid_grad, mlp_grad, gate_grad)); gradients are
@@ -1105,8 +1105,20 @@ class FusedMLRenderer:
         loss's depth-mutual term then covers the live pairs only, its cv^2
         term still the softmax gate's importance, and last_forward also holds
         gate_used, live and route_count ((K,) int32 on the device: the rays
-        routed to each sub-NeRF)."""
+        routed to each sub-NeRF).
+        ray_weight ((B,) fp32): per-ray importance weights of a batch that was
+        not drawn uniformly (sampler.GuidedSampler).  One launch between the
+        loss and the backward (rn_guided_epilogue) multiplies the seeds on
+        rgb, opacity and depth by them, and the distortion seed becomes the
+        [K][B] tensor lambda ray_weight / B; dL_dgate from the loss (the cv^2
+        term, a batch statistic) stays unweighted, and so do the returned
+        terms: they are the means a log compares across runs.  guided: a
+        (GuidedSampler, cell_idx) pair; the same launch then records each
+        ray's unweighted squared rgb error in the sampler's accumulators.
+        ray_weight=None launches nothing extra."""
         from .losses import fused_nerf_loss
+        if guided is not None and ray_weight is None:
+            raise ValueError("train_step: guided=(sampler, cell_idx) needs ray_weight")
         dist = lambda_distortion > 0
         rgb, opacity, depth, gate, imp = self.forward(rays_o, rays_d, gate_in2, noise, bg,
                                                       T_threshold, exp_step_factor, dist,
@@ -1125,6 +1137,14 @@ class FusedMLRenderer:
             self.ws.dist_k if dist else None, deterministic=self.deterministic,
             live=None if rt is None else rt["live"])
         d_dist = float(lambda_distortion) / rays_o.shape[0] if dist else None
+        if ray_weight is not None:
+            from .sampler import guided_epilogue
+            gs, cells = (None, None) if guided is None else guided
+            guided_epilogue(rgb, target_rgb, cells, ray_weight, d_depth.shape[1],
+                            None if gs is None else gs.acc_sum,
+                            None if gs is None else gs.acc_cnt, d_rgb, d_op, d_depth)
+            if dist:
+                d_dist = (ray_weight * d_dist).expand(self.model.size, -1).contiguous()
         if not input_grad:
             grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
                                   d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist)

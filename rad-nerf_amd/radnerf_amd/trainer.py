@@ -129,7 +129,9 @@ class Trainer:
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
                  optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None, intrinsics=None,
                  cull_invisible=False, erode=False, deterministic=False, gate_topk=None,
-                 gate_min=0.0, renormalize=False, route_from_step=0):
+                 gate_min=0.0, renormalize=False, route_from_step=0, guided=False,
+                 guided_tile=16, guided_uniform_frac=0.5, guided_alpha=0.5,
+                 guided_refresh_every=16):
         """gate_topk / gate_min / renormalize: routed training (FusedMLRenderer.
         forward; DESIGN.md §4 "Routed training") -- every step from global_step
         route_from_step on marches and differentiates only the (ray, sub-NeRF)
@@ -145,7 +147,18 @@ class Trainer:
         one GPU in one process (step / step_pixels without `noise` still draw
         from torch's generator: seed it).  Under data parallelism each rank's
         local gradient is reproducible; the collective sums the ranks in
-        RCCL's order, which this mode does not fix."""
+        RCCL's order, which this mode does not fix.
+        guided=True: step_sampled / fit draw their batches through
+        sampler.GuidedSampler (DESIGN.md §4 "Error-guided sampling") -- a
+        share guided_uniform_frac of the rays uniformly, the rest in
+        proportion to a guided_tile-pixel tiled map of the recent rgb error,
+        every ray's seeds divided by its sampling density; the map moves by
+        guided_alpha towards the recorded errors every guided_refresh_every
+        steps.  Needs images and img_wh; ValueError for guided_uniform_frac
+        outside (0, 1] (at 0 a pixel of a cell the map has written off would
+        never be seen again), for the sampler's own limits, and under data
+        parallelism (the ranks' maps would diverge).  step, step_pixels and
+        validate are unchanged: their callers choose their own pixels."""
         if optimize_ext and (directions is None or poses is None):
             raise ValueError("Trainer(optimize_ext=True) needs directions (P, 3) and poses "
                              "(N, 3, 4): the pose corrections are per image of `poses`")
@@ -177,6 +190,31 @@ class Trainer:
                 raise ValueError(f"Trainer: images are {images.n_images} x {images.n_pix} pixels "
                                  f"for {poses.shape[0]} poses and {directions.shape[0]} rows of "
                                  "directions")
+        self.guided = None
+        self._guided_args = None
+        if guided:
+            from .sampler import guided_geometry
+            fn = "Trainer(guided=True)"
+            if images is None or img_wh is None:
+                raise ValueError(f"{fn} needs images and img_wh (W, H): the error map is tiled "
+                                 "over the training images")
+            if not 0.0 < float(guided_uniform_frac) <= 1.0:
+                raise ValueError(f"{fn}: guided_uniform_frac must be in (0, 1], got "
+                                 f"{guided_uniform_frac!r}")
+            if not 0.0 < float(guided_alpha) <= 1.0:
+                raise ValueError(f"{fn}: guided_alpha must be in (0, 1], got {guided_alpha!r}")
+            if isinstance(guided_refresh_every, bool) \
+                    or not isinstance(guided_refresh_every, numbers.Integral) \
+                    or guided_refresh_every < 1:
+                raise ValueError(f"{fn}: guided_refresh_every must be an int >= 1, got "
+                                 f"{guided_refresh_every!r}")
+            guided_geometry(fn, images.n_images, images.n_pix, img_wh, guided_tile)
+            if _world() > 1:
+                raise ValueError(f"{fn} does not run under data parallelism (world size "
+                                 f"{_world()}): each rank would build its own map")
+            self._guided_args = dict(tile=int(guided_tile), uniform_frac=float(guided_uniform_frac),
+                                     alpha=float(guided_alpha))
+        self.guided_refresh_every = int(guided_refresh_every) if guided else 0
         # (one sub-NeRF: nothing to route, the arguments are accepted and ignored)
         route_params("Trainer", gating_net.out_dim, gate_topk, gate_min, renormalize)
         if isinstance(route_from_step, bool) or not isinstance(route_from_step, numbers.Integral) \
@@ -252,6 +290,11 @@ class Trainer:
         self.n_culled = None
         if cull_invisible:
             self.n_culled = model.mark_invisible_cells(intrinsics, self.poses, self.img_wh)
+        if self._guided_args is not None:
+            from .sampler import GuidedSampler
+            self.guided = GuidedSampler(images, self.img_wh, **self._guided_args)
+        # steps recorded in the guided sampler's accumulators since its last refresh
+        self._guided_pending = False
 
     @property
     def routing(self):
@@ -313,18 +356,33 @@ class Trainer:
         if self.mean_dir is None and self.gate.type == "image":
             self.mean_dir = self.directions.mean(0).contiguous()
         ext = self.optimize_ext
-        b = self.last_batch = sample_batch(
-            self.images, self.directions, self.poses, self.n_rays, self.model.size, self.seed,
+        gs = getattr(self, "guided", None)
+        if gs is None:
+            draw, head = sample_batch, (self.images,)
+        else:
+            # the map follows the errors recorded since its last refresh,
+            # before this step's batch is drawn from it
+            if self.global_step % self.guided_refresh_every == 0 and self._guided_pending:
+                gs.refresh()
+                self._guided_pending = False
+            draw, head = gs.sample, ()
+        b = self.last_batch = draw(
+            *head, self.directions, self.poses, self.n_rays, self.model.size, self.seed,
             self.global_step, rank=_rank(),
             dR=self.dR.detach() if ext else None, dT=self.dT.detach() if ext else None,
             mean_dir=self.mean_dir if self.gate.type == "image" else None, out=self.last_batch)
         # ml_rendering.py:192-198: the random background only with exp stepping
         bg = b["bg"] if self.random_bg and self.esf != 0 else self._bg()
-        return self._step(b["rays_o"], b["rays_d"], b["imgs_d"], b["target"],
-                          b["noise"] if noise is None else noise,
-                          (b["img_idxs"], b["pix_idxs"]) if ext else None, bg)
+        weights = {} if gs is None else dict(ray_weight=b["ray_weight"],
+                                             guided=(gs, b["cell_idx"]))
+        terms = self._step(b["rays_o"], b["rays_d"], b["imgs_d"], b["target"],
+                           b["noise"] if noise is None else noise,
+                           (b["img_idxs"], b["pix_idxs"]) if ext else None, bg, weights)
+        if gs is not None:
+            self._guided_pending = True
+        return terms
 
-    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks, bg=None):
+    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks, bg=None, weights=None):
         if self.global_step % self.update_interval == 0:
             rdist.update_density_grid(self.model, 0.01 * MAX_SAMPLES / 3 ** 0.5,
                                       self.global_step,
@@ -342,13 +400,14 @@ class Trainer:
             terms, _ = self.renderer.train_step(rays_o, rays_d, second, target_rgb, noise,
                                                 bg, exp_step_factor=self.esf,
                                                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2],
-                                                **self.lambdas, **self._route_now())
+                                                **self.lambdas, **self._route_now(),
+                                                **(weights or {}))
         else:
             from . import rays as R
             terms, _, (g_o, g_d, g_2) = self.renderer.train_step(
                 rays_o, rays_d, second, target_rgb, noise, bg, exp_step_factor=self.esf,
                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2], input_grad=True, **self.lambdas,
-                **self._route_now())
+                **self._route_now(), **(weights or {}))
             # the gate's second input is rays_d ("ray") or imgs_d ("image")
             if self.gate.type == "image":
                 g_i = g_2.contiguous()
@@ -411,6 +470,13 @@ class Trainer:
         route = self._route_hyper()
         if route != self._dense_hyper():
             h.update(route)
+        # likewise the guided sampler's: absent from an unguided trainer's state
+        gs = getattr(self, "guided", None)
+        if gs is not None:
+            h.update({"guided": True, "guided_tile": int(gs.tile),
+                      "guided_uniform_frac": float(gs.uniform_frac),
+                      "guided_alpha": float(gs.alpha),
+                      "guided_refresh_every": int(self.guided_refresh_every)})
         for i, g in enumerate(self.opt.param_groups):
             h[f"adam.{i}.betas"] = [float(b) for b in g["betas"]]
             h[f"adam.{i}.eps"] = float(g["eps"])
@@ -432,6 +498,12 @@ class Trainer:
         state = {"structure": self._structure(), "hyper": self._hyper(), "model": model}
         if self.optimize_ext:
             state["poses"] = {"dR": fetch("poses/dR", self.dR), "dT": fetch("poses/dT", self.dT)}
+        gs = getattr(self, "guided", None)
+        if gs is not None:
+            # the map and what was recorded since its last refresh; w and cdf
+            # are recomputed on load
+            state["guided"] = {k: fetch("guided/" + k, getattr(gs, k))
+                               for k in ("emap", "acc_sum", "acc_cnt")}
         per_param = {}
         for name, p in self._named_params():
             st = self.opt.state.get(p) or {}
@@ -516,6 +588,13 @@ class Trainer:
                 raise ValueError(f"{where}: count_grid is {tuple(count.shape)}")
             global_step = int(state["progress"]["global_step"])
             gens = state["generators"]
+            gs = getattr(self, "guided", None)
+            # (a state of the other kind got here under override=True: this
+            # trainer's sampling stands, a guided one starts a fresh map)
+            gmap = state.get("guided") if gs is not None else None
+            if gmap is not None:
+                gmap = {k: match(getattr(gs, k), gmap[k], "guided/" + k)
+                        for k in ("emap", "acc_sum", "acc_cnt")}
         except KeyError as e:
             raise ValueError(f"{where}: the state has no {e.args[0]!r}") from e
         # everything checked: write
@@ -529,6 +608,14 @@ class Trainer:
                                  "exp_avg_sq": sq.to(dev, copy=True)}
         for g, lr in zip(self.opt.param_groups, lrs):
             g["lr"] = lr
+        if gs is not None:
+            if gmap is None:
+                gs.reset()
+            else:
+                gs.load_state_dict(gmap)
+            # a refresh of empty accumulators changes nothing, so the first
+            # step at a refresh boundary may always run one
+            self._guided_pending = True
         self.global_step = global_step
         self._fit_progress = copy.deepcopy(state["progress"].get("fit"))
         torch.set_rng_state(gens["cpu"])
