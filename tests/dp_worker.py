@@ -50,10 +50,7 @@ def hooked_split_schedule(rank, dev, stream_ordered=True, force=False):
     B, K, scale = 512, 2, 16.0
     model = MNGP(scale, size=K, seed=5).to(dev)
     gate = Ray_Gate(K, seed=6).to(dev)
-    bits = S.bitfields(K, model.cascades, p=0.5, seed=7)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(model, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
+    S.set_bitfields(model, S.bitfields(K, model.cascades, p=0.5, seed=7))
     bg = torch.zeros(3, device=dev)
     r = FusedMLRenderer(model, gate, B)
     r.grid_fx = r.grid_bin = True            # (512 x 2 rays: fp32 by the renderer's choice)
@@ -114,13 +111,8 @@ def main(out_path):
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     B, K, scale = 1024, 2, 0.5
-    model = MNGP(scale, size=K, seed=3).to(dev)
-    gate = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, model.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(model, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    bg = torch.ones(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    model, gate, bg = sc.m, sc.g, sc.bg
     params = [model.xyz_encoder.params, model.mlp_params, gate.params]
     r = FusedMLRenderer(model, gate, B)
     ar = rdist.GradAllReduce(params, dev)

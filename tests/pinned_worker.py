@@ -14,7 +14,6 @@ import torch.distributed as dist  # noqa: E402
 from radnerf_amd import dist as rdist  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 from radnerf_amd.pinned import PinnedMLRenderer  # noqa: E402
 
 
@@ -28,17 +27,9 @@ def main(out_path):
     dev = torch.device("cuda", 0)
     B, K = int(os.environ.get("PIN_RAYS", 2048)), int(os.environ.get("PIN_K", 2))
     scale = float(os.environ.get("PIN_SCALE", 0.5))
-    esf = 1 / 256 if scale > 0.5 else 0.0
-    model = MNGP(scale, size=K, seed=3).to(dev)
-    gate = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, model.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(model, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale, seed=0))
-    noise = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
-    g_rgb, g_op, g_depth = (torch.from_numpy(s).to(dev) for s in S.loss_seeds(B, K, seed=4))
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    model, gate, o, d, noise, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg, sc.esf
+    g_rgb, g_op, g_depth = sc.seeds
 
     r = PinnedMLRenderer(model, gate, B)
     ar = rdist.GradAllReduce([model.xyz_encoder.params, model.mlp_params, gate.params], dev)

@@ -19,9 +19,10 @@ import pytest
 import torch
 
 from radnerf_amd import layout as LY
+from radnerf_amd import synthetic as S
 from radnerf_amd._lib import lib
 from radnerf_amd.fused import get_renderer, ml_render_fused, release_renderers
-from test_gpu_ml import FX_LEVEL_TOL, _run, _setup, check_fx_vs_fp32
+from test_gpu_ml import FX_LEVEL_TOL, _run, check_fx_vs_fp32
 
 pytestmark = pytest.mark.gpu
 
@@ -125,7 +126,8 @@ def _levels(g, lv):
 @pytest.mark.parametrize("B,K,scale", [(1024, 4, 16.0), (2048, 2, 0.5)])
 def test_binned_matches_fp32_and_is_reproducible(cuda, B, K, scale):
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     assert r.grid_fx
     assert r.grid_bin == (scale > 0.5)
@@ -145,7 +147,8 @@ def test_binned_matches_fp32_and_is_reproducible(cuda, B, K, scale):
 
 def test_binned_record_overflow_redo(cuda):
     B, K, scale = 1024, 4, 16.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     assert r.grid_bin
     _, g32 = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, 1 / 256)
@@ -164,7 +167,8 @@ def test_binned_record_overflow_redo(cuda):
 
 def test_binned_pool_overflow_redo_then_grows(cuda):
     B, K, scale = 1024, 4, 16.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     r.bin_records_per_pair = 8           # a pool far too small for the step
     r.bin_f32_levels = 0                 # (every level takes pages: each wave opens two)
@@ -358,7 +362,8 @@ def test_renderer_raises_on_sum_fault(cuda):
     later raise RuntimeError instead of stepping on a partial gradient.  A clean
     run leaves the word 0."""
     B, K, scale = 1024, 2, 16.0               # (rays x sub-NeRFs > 1024: fixed point)
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     assert r.grid_bin
     for _ in range(4):
@@ -380,7 +385,8 @@ def test_binned_default_coarse_levels_fp32(cuda, B, K):
     gradient of the same step (FX_LEVEL_TOL), the binned levels are bitwise
     identical step to step, the coarse levels took no pages."""
     scale = 16.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     n = r.bin_f32_levels
     assert r.grid_bin and n == (9 if K >= 8 else 8)

@@ -60,25 +60,14 @@ _SCENES = {}
 
 
 def _scene(cuda, B, K, scale):
-    """model, gate and one batch, as tests/test_gpu_ml.py::_setup (occupancy
-    p = 0.5); built once per shape and never written to"""
+    """model, gate and one batch of synthetic.parity_scene (occupancy p = 0.5);
+    built once per shape and never written to"""
     key = (B, K, scale)
     if key not in _SCENES:
-        m = MNGP(scale, size=K, seed=3)
-        g = Ray_Gate(K, seed=2)
-        with torch.no_grad():
-            m.xyz_encoder.params.copy_(
-                torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-            m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-            g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-            bits = S.bitfields(K, m.cascades, p=0.5)
-            for i in range(K):
-                getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-        m, g = m.to(cuda), g.to(cuda)
-        o, d = S.rays(B, scale)
+        ps = S.parity_scene(K, B, scale=scale, device=cuda)
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
         gen = torch.Generator().manual_seed(11)
-        _SCENES[key] = dict(m=m, g=g, o=to(o), d=to(d), noise=to(S.noise(K, B)),
+        _SCENES[key] = dict(m=ps.m, g=ps.g, o=to(ps.o), d=to(ps.d), noise=to(ps.noise),
                             target=torch.rand(B, 3, generator=gen).to(cuda),
                             bg=torch.ones(3, device=cuda),
                             esf=1 / 256 if scale > 0.5 else 0.0)

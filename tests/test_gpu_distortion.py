@@ -30,7 +30,6 @@ from radnerf_amd.losses import DistortionLoss, NeRFLoss
 from radnerf_amd.networks import NGP
 from radnerf_amd.pinned import PinnedMLRenderer
 from radnerf_amd.rendering import ml_render, render
-from test_gpu_ml import _setup
 
 pytestmark = pytest.mark.gpu
 
@@ -272,7 +271,8 @@ _rel = lambda a, b: float((a - b).norm() / b.norm().clamp_min(1e-30))
 def test_fused_vs_opbyop_autograd(cuda, scale, K, B):
     esf = 1 / 256 if scale > 0.5 else 0.0
     lam = LAMBDA[scale]
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     args = (m, g, o, d, noise, seeds, cuda, esf)
     _, g0 = _loss_backward(ml_render, *args, 0.0, fused=False)
     rd, gd = _loss_backward(ml_render, *args, lam, fused=False, distortion=True)
@@ -306,7 +306,7 @@ def test_render_single_ngp(cuda):
     with torch.no_grad():
         m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(S.mlp_params(1, LY.FIELD_PARAMS)))
-        m.density_bitfield_0.copy_(torch.from_numpy(S.bitfields(1, m.cascades, p=0.5)[0]))
+    S.set_bitfields(m, S.bitfields(1, m.cascades, p=0.5))
     m = m.to(cuda)
     o, d = (torch.from_numpy(a).to(cuda) for a in S.rays(B, scale))
     nz = torch.from_numpy(S.noise(1, B)[0]).to(cuda)
@@ -349,7 +349,8 @@ def test_train_step_matches_autograd(cuda, B, K, scale):
     # ((rgb - target) 2 / 3B with B = 512)
     lambdas = dict(lambda_opacity=1e-3, lambda_cv_importance=1e-2, lambda_depth_mutual=5e-2,
                    lambda_distortion=LAMBDA[scale])
-    m, g, o, d, noise, _, _ = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise = sc.m, sc.g, sc.o, sc.d, sc.noise
     o, d, nz = (torch.from_numpy(a).to(cuda) for a in (o, d, noise))
     tgt = torch.rand(B, 3, generator=torch.Generator().manual_seed(5)).to(cuda)
     ref = None
@@ -382,7 +383,8 @@ def test_train_step_matches_autograd(cuda, B, K, scale):
 
 def test_default_step_unchanged_by_a_distortion_step(cuda):
     B, K = 256, 2
-    m, g, o, d, noise, seeds, _ = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds
     o, d, nz = (torch.from_numpy(a).to(cuda) for a in (o, d, noise))
     sd = [torch.from_numpy(s).to(cuda) for s in seeds]
     bg = torch.ones(3, device=cuda)
@@ -423,7 +425,8 @@ def test_default_step_unchanged_by_a_distortion_step(cuda):
 
 def test_pinned_refuses_distortion(cuda):
     B, K = 64, 2
-    m, g, o, d, noise, seeds, _ = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds
     o, d, nz = (torch.from_numpy(a).to(cuda) for a in (o, d, noise))
     bg = torch.ones(3, device=cuda)
     r = PinnedMLRenderer(m, g, B)

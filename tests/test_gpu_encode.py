@@ -267,8 +267,7 @@ def _scene(cuda, scale):
         m.xyz_encoder.params.copy_(torch.from_numpy(table.astype(np.float32)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(ER.transparent_mlp(K, ER.transparent_a(K))))
         g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
+    S.set_bitfields(m, bits)
     o, d = ER.lattice_rays(scale, lv)
     return lv, m.to(cuda), g.to(cuda), table, bits, o, d, S.noise(K, len(o))
 

@@ -14,13 +14,13 @@ import pytest
 import torch
 
 import metrics_ref as MR
-from radnerf_amd import layout as LY
 from radnerf_amd import synthetic as S
 from radnerf_amd.evaluate import ImageEvaluator
-from radnerf_amd.networks import MNGP, NGP, Ray_Gate
+from radnerf_amd.networks import NGP
 from radnerf_amd.rays import batch_rays
 from radnerf_amd.rendering import NEAR_DISTANCE, ml_render, render
 from radnerf_amd.trainer import Trainer
+from test_gpu_render import _init
 
 pytestmark = pytest.mark.gpu
 
@@ -46,27 +46,16 @@ def _camera(scale, n_poses=2, half=0.6):
     return dirs, poses.contiguous()
 
 
-def _init(m, K, p=0.3):
-    """as tests/test_gpu_render.py::_init"""
-    with torch.no_grad():
-        m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        bits = S.bitfields(K, m.cascades, p=p)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-
-
 def _setup(cuda, K, gate_type, scale):
     if gate_type is None:
         m, g = NGP(scale, seed=3), None
+        _init(m, p=0.3)
+        m = m.to(cuda)
     else:
-        m, g = MNGP(scale, size=K, seed=3), Ray_Gate(K, type=gate_type, seed=2)
-        with torch.no_grad():
-            g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        g = g.to(cuda)
-    _init(m, K)
+        sc = S.parity_scene(K, scale=scale, p=0.3, gate_type=gate_type, device=cuda)
+        m, g = sc.m, sc.g
     dirs, poses = _camera(scale)
-    return m.to(cuda), g, dirs.to(cuda), poses.to(cuda)
+    return m, g, dirs.to(cuda), poses.to(cuda)
 
 
 CASES = [(1, None), (2, "ray"), (2, "image")]

@@ -16,8 +16,9 @@ import pytest
 import torch
 
 from radnerf_amd import layout as LY
+from radnerf_amd import synthetic as S
 from radnerf_amd.fused import get_renderer, ml_render_fused
-from test_gpu_ml import _run, _setup, check_fx_vs_fp32
+from test_gpu_ml import _run, check_fx_vs_fp32
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +36,8 @@ def _level(g, lv, l):
 @pytest.mark.parametrize("B,K,scale", [(2048, 2, 0.5), (1024, 4, 16.0)])
 def test_fx_matches_fp32_and_is_reproducible(cuda, B, K, scale):
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     assert r.grid_fx
     r.bin_f32_levels = 0          # (scale 16: every level fixed point, binned)
@@ -59,7 +61,8 @@ def test_fx_matches_fp32_and_is_reproducible(cuda, B, K, scale):
 
 def test_fx_overflow_redo(cuda):
     B, K, scale = 1024, 2, 0.5
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     _, g32 = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, 0.0)
     acc, scales, vmax, redo = r.ws._fx
@@ -84,7 +87,8 @@ def test_fx_overflow_redo(cuda):
 
 def test_fx_nonfinite_seed_propagates(cuda):
     B, K = 512, 2
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     r.grid_fx = True                 # (512 rays x 2: fp32 by the renderer's own choice)
     _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, 0.0)      # fp32 step: scales
@@ -111,7 +115,8 @@ def test_fx_entry_wrap_sets_redo(cuda):
     level's exact entry sum then differs from its record sum by a multiple of
     2^32, the redo flag is set, and the result is the fp32 one."""
     B, K = 8192, 2
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     o = np.repeat(o[:1], B, 0)
     d = np.repeat(d[:1], B, 0)
     seeds = tuple(np.abs(s).astype(np.float32) for s in seeds)
@@ -163,7 +168,8 @@ def test_fx_per_entry_agreement(cuda, capsys, B, K, scale, f32_levels, bar):
     per-entry deviation may not exceed."""
     from radnerf_amd.optim import FusedAdam
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     assert r.grid_fx and r.grid_bin == (scale > 0.5)
     r.fx_f32_levels = f32_levels

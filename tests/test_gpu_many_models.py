@@ -23,7 +23,6 @@ from radnerf_amd.fused import get_renderer, ml_render_fused
 from radnerf_amd.networks import Ray_Gate
 from radnerf_amd.rendering import ml_render as _ml_render
 from parity import GATE_TOL, check_grads, rel
-from tests_parity_helpers import setup_ml
 
 pytestmark = pytest.mark.gpu
 
@@ -343,7 +342,8 @@ def test_chain_defaults_vs_dropin_vs_oracle(cuda, monkeypatch, scale, K, B):
     gradients per grid level / MLP layer / gate within parity.check_grads'
     bars.  Measured: DESIGN.md §2."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = setup_ml(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     if K > 8:
         assert (r.merged_bwd, r.merged_fwd, r.level_fwd) == (False, False, False)
@@ -424,7 +424,8 @@ def test_image_evaluator_nine_models(cuda):
     from radnerf_amd.evaluate import ImageEvaluator
     from radnerf_amd.rays import batch_rays
     K, scale, (W, H) = 9, 0.5, (16, 12)
-    m, g, _, _, _, _, bits = setup_ml(cuda, B=8, K=K, scale=scale, p=0.3)
+    sc = S.parity_scene(K, 8, scale=scale, p=0.3, device=cuda)
+    m, g, bits = sc.m, sc.g, sc.bits
     dirs, pose = _camera(W, H, scale)
     dirs, pose = dirs.to(cuda), pose.to(cuda)
     N = W * H
@@ -468,7 +469,8 @@ def test_per_model_backward_calls_hooks(cuda, K, per_model_by_hand):
     does not promise), and to the float-atomic order bar of test_gpu_ml.py
     (1e-5 relative) otherwise."""
     B = 72
-    m, g, o, d, noise, seeds, _ = setup_ml(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds
     r = get_renderer(m, g, B)
     if per_model_by_hand:
         r.merged_bwd = False

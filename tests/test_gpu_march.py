@@ -326,8 +326,7 @@ def _model(cuda, scale, K, p):
     with torch.no_grad():
         m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.tensor(bits[i]))
+    S.set_bitfields(m, bits)
     assert m.cascades == M.cascades_of(scale) and m.grid_size == M.GRID
     return m.to(cuda)
 

@@ -17,7 +17,6 @@ from oracle import ml_oracle
 from radnerf_amd import layout as LY
 from radnerf_amd import synthetic as S
 from radnerf_amd.fused import ml_render_fused, get_renderer
-from radnerf_amd.networks import MNGP, Ray_Gate
 from radnerf_amd.rendering import ml_render as _ml_render
 from parity import LAYERS, check_grads, rel as _rel  # noqa: F401
 
@@ -27,23 +26,6 @@ def ml_render(*a, **kw):
     return _ml_render(*a, fused=False, **kw)
 
 pytestmark = pytest.mark.gpu
-
-
-def _setup(cuda, B=384, K=2, scale=0.5, p=0.5):
-    m = MNGP(scale, size=K, seed=3)
-    g = Ray_Gate(K, seed=2)
-    with torch.no_grad():
-        m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        bits = S.bitfields(K, m.cascades, p=p)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    m, g = m.to(cuda), g.to(cuda)
-    o, d = S.rays(B, scale)
-    noise = S.noise(K, B)
-    seeds = S.loss_seeds(B, K)
-    return m, g, o, d, noise, seeds, bits
 
 
 def _run(fn, m, g, o, d, noise, seeds, cuda, esf):
@@ -119,7 +101,8 @@ def check_used_vs_oracle(w, ores, thr=1e-4):
                                        (16.0, 4, 384), (16.0, 8, 256)])
 def test_fused_vs_dropin_vs_oracle(cuda, scale, K, B):
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, scale=scale, K=K)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     # fixed point is the renderer's choice above 1024 rays x sub-NeRFs; these
     # oracle-sized batches check it too
     get_renderer(m, g, len(o)).grid_fx = True
@@ -170,7 +153,8 @@ def test_workspace_reuse_is_caught(cuda):
     one's backward raises; a no_grad render in between uses its own workspace
     and leaves the gradients unchanged."""
     B, K = 256, 2
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, 0.0)    # fp32 step (fx scales)
     _, ref = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, 0.0)
     to = lambda a: torch.from_numpy(a).to(cuda)
@@ -195,7 +179,8 @@ def test_fused_vs_dropin_ragged(cuda, B, K, scale):
     reference-structured drop-in chain, outputs and gradients.  K = 12: the
     per-model field kernels (no merged kernel above 8 sub-NeRFs)."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     rf, gf = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, esf)
     rd, gd = _run(ml_render, m, g, o, d, noise, seeds, cuda, esf)
     for k in ("rgb", "opacity", "depth", "gating_code"):
@@ -212,7 +197,8 @@ def test_fused_full_size_properties(cuda, B, K, scale):
     8192 x K = 8, scale 16): size-independent properties, and the backward's
     gradients finite with the merged order a permutation."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     to = lambda a: torch.from_numpy(a).to(cuda)
     res = ml_render_fused(m, g, to(o), to(d), to(d), noise=to(noise), exp_step_factor=esf)
     r = get_renderer(m, g, B)
@@ -264,7 +250,8 @@ def test_full_size_fx_vs_fp32(cuda, B, K, scale):
     MLP and gate gradients unchanged; then two more default steps with
     identical inputs give identical bits (exact integer sums)."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     assert r.grid_fx and r.grid_bin == (scale > 0.5)
     _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, esf)        # fp32: measures the scales
@@ -292,7 +279,8 @@ def test_full_size_fx_vs_fp32(cuda, B, K, scale):
 
 def _merged_vs_split(cuda, B, K, scale, p=0.5):
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale, p=p)
+    sc = S.parity_scene(K, B, scale=scale, p=p, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     out = []
     for merged in (True, False):
@@ -339,7 +327,8 @@ def test_merged_backward_chunking(cuda):
     """Small chunks (many queue grabs, single-ray chunks above max_chunk) and
     ramps of head chunks give the same gradients."""
     B, K = 2048, 2
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     res = []
     _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, 0.0)    # fp32 step (fx scales)
@@ -400,7 +389,8 @@ def test_chunk_schedule(cuda, B, K, scale, mc, bal, head):
     big chunks to take than the others (C4 at 2560 left a few blocks one big
     chunk behind the rest).  head: the ramp of head chunks (None: the
     renderer's default, a ramp to max_chunk at scale 0.5)."""
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     esf = 1.0 / 256 if scale > 0.5 else 0.0
     r = get_renderer(m, g, B)
     head0 = r.head_chunk
@@ -438,7 +428,8 @@ def test_merged_forward_matches_per_model(cuda, B, K, scale):
     in merged order or per tile) vs rn_field_fwd: identical per-sample
     arithmetic, so sigma / rgb and the encoding cache are bit-exact."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     to = lambda a: torch.from_numpy(a).to(cuda)
     outs = []
@@ -469,7 +460,8 @@ def test_level_forward_launch_shapes(cuda, enc_blocks, mlp_blocks):
     every tile of its two levels), ragged splits and more blocks than tiles:
     bit-exact with the merged forward."""
     B, K = 2048, 3
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=16.0)
+    sc = S.parity_scene(K, B, scale=16.0, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     to = lambda a: torch.from_numpy(a).to(cuda)
     outs = []
@@ -501,7 +493,8 @@ def test_merged_forward_chunking(cuda, mc, blocks, threads):
     MLP tiles of chunk i - 1) over many small chunks per block, ragged chunks
     and few blocks: still bit-exact with the per-model kernel."""
     B, K = 2048, 3
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K)
+    sc = S.parity_scene(K, B, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     to = lambda a: torch.from_numpy(a).to(cuda)
     outs = []
@@ -544,7 +537,8 @@ def test_int_grad_matches_fp32(cuda, B, K, scale):
     carries) vs fp32 atomics: equal up to the 2^-26-of-max-seed quantisation;
     bitwise reproducible across runs."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     r.int_grad = False
     _, gf = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, esf)
@@ -567,7 +561,8 @@ def test_input_grads_vs_oracle(cuda, scale, K, B):
     rn_raymarching_train_bw): fused chain and drop-in chain vs the oracle's
     autograd + segment sums (custom_functions.py:102-112)."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     to = lambda a: torch.from_numpy(a).to(cuda)
     out = {}
     for name, fn in (("fused", ml_render_fused), ("dropin", ml_render)):
@@ -598,7 +593,8 @@ def test_fused_mostly_empty_rays(cuda, K):
     the merged backward stages in LDS (1,536), which then looks rays up in
     global memory.  Fused chain vs the drop-in chain: outputs and gradients."""
     B, scale = 8192, 0.5
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     o = o.copy()
     d = d.copy()
     away = np.arange(B) % 8 != 0
@@ -622,7 +618,8 @@ def test_plan_writes_level_forward_input(cuda, B, K, scale):
     the separate prep pass of rn_field_fwd_levels (K = 2: the two-run merge;
     K = 8: the merge tree; K = 1: the rank path)."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     to = lambda a: torch.from_numpy(a).to(cuda)
     preps = []

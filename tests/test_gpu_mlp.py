@@ -421,8 +421,7 @@ def _chain_scene(cuda, scale, flats):
         m.xyz_encoder.params.copy_(torch.from_numpy(c.table.astype(np.float32)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(np.stack(flats)))
         g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
+    S.set_bitfields(m, bits)
     o, d = ER.lattice_rays(scale, c.lv)
     return m.to(cuda), g.to(cuda), o, d, S.noise(K, len(o)), S.loss_seeds(len(o), K)
 

@@ -17,7 +17,6 @@ import torch
 
 from radnerf_amd import synthetic as S
 from radnerf_amd.fused import FusedMLRenderer
-from radnerf_amd.networks import MNGP, Ray_Gate
 from radnerf_amd.pinned import PinnedMLRenderer
 
 pytestmark = pytest.mark.gpu
@@ -30,16 +29,8 @@ def _rel(a, b):
 
 def test_pinned_single_rank_matches_fused(cuda):
     B, K = 1024, 2
-    m = MNGP(0.5, size=K, seed=3).to(cuda)
-    g = Ray_Gate(K, seed=4).to(cuda)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(cuda) for a in S.rays(B, 0.5, seed=0))
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(cuda)
-    sd = [torch.from_numpy(s).to(cuda) for s in S.loss_seeds(B, K, seed=4)]
-    bg = torch.ones(3, device=cuda)
+    sc = S.bench_scene(K, B, 0.5, cuda)
+    m, g, o, d, nz, sd, bg = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bg
     outs, grads = [], []
     for cls in (FusedMLRenderer, PinnedMLRenderer):
         r = cls(m, g, B)

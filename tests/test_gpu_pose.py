@@ -9,12 +9,10 @@ tests and in fp32 on the device for the chain test.
 import pytest
 import torch
 
-from radnerf_amd import layout as LY
 from radnerf_amd import synthetic as S
 from radnerf_amd._lib import lib
 from radnerf_amd.fused import get_renderer, ml_render_fused
 from radnerf_amd.losses import NeRFLoss
-from radnerf_amd.networks import MNGP, Ray_Gate
 from radnerf_amd.rays import batch_rays, pose_rays, pose_rays_backward
 from radnerf_amd.trainer import Trainer
 
@@ -193,40 +191,6 @@ def test_pose_rays_autograd(kcase, cuda):
 
 
 # ------------------------------------------------------------------- 3. chain
-def _setup(cuda, K, gate_type, scale=0.5, p=0.5, rough_grid=True):
-    m = MNGP(scale, size=K, seed=3)
-    g = Ray_Gate(K, type=gate_type, seed=2)
-    with torch.no_grad():
-        if rough_grid:      # white noise of amplitude 0.1; else the module's own init
-            m.xyz_encoder.params.copy_(
-                torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        bits = S.bitfields(K, m.cascades, p=p)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    return m.to(cuda), g.to(cuda)
-
-
-def _ring_cameras(n_img, res=24, radius=1.5, half=0.3, seed=0):
-    """n_img cameras on a ring around the origin, looking at it (c2w columns
-    right / up / forward), res x res unit pixel directions of half-width
-    `half` at unit depth."""
-    u = torch.linspace(-half, half, res)
-    y, x = torch.meshgrid(u, u, indexing="ij")
-    dirs = torch.stack([x.reshape(-1), y.reshape(-1), torch.ones(res * res)], -1)
-    dirs = dirs / dirs.norm(dim=1, keepdim=True)
-    ang = torch.arange(n_img) * (2 * torch.pi / n_img) + 0.3
-    pos = torch.stack([radius * torch.cos(ang), radius * torch.sin(ang),
-                       0.4 * torch.sin(3 * ang)], -1)
-    fwd = -pos / pos.norm(dim=1, keepdim=True)
-    right = torch.linalg.cross(fwd, torch.tensor([0.0, 0.0, 1.0]).expand_as(fwd))
-    right = right / right.norm(dim=1, keepdim=True)
-    up = torch.linalg.cross(right, fwd)
-    poses = torch.cat([torch.stack([right, up, fwd], 2), pos[:, :, None]], 2)
-    return dirs.contiguous(), poses.contiguous()
-
-
 @pytest.mark.parametrize("gate_type", ["ray", "image"])
 def test_train_step_pose_gradients_match_autograd(cuda, gate_type):
     """The two chains form their rays with different roundings (measured
@@ -246,8 +210,9 @@ def test_train_step_pose_gradients_match_autograd(cuda, gate_type):
     gradients are autograd's (asserted below), and the pose backward is within
     1e-5 of fp64 (test 1)."""
     B, K, N = 256, 2, 5
-    m, g = _setup(cuda, K, gate_type, p=1.0, rough_grid=False)
-    dirs, poses = (t.to(cuda) for t in _ring_cameras(N))
+    sc = S.parity_scene(K, p=1.0, gate_type=gate_type, rough_grid=False, device=cuda)
+    m, g = sc.m, sc.g
+    dirs, poses = (t.to(cuda) for t in S.ring_cameras(N, 24))
     gen = torch.Generator().manual_seed(7)
     dR0 = (0.02 * torch.randn(N, 3, generator=gen)).to(cuda)
     dT0 = (0.02 * torch.randn(N, 3, generator=gen)).to(cuda)
@@ -330,8 +295,9 @@ def test_train_step_pose_gradients_match_autograd(cuda, gate_type):
 @pytest.mark.parametrize("gate_type", ["ray", "image"])
 def test_trainer_step_pixels(cuda, gate_type):
     B, K, N, lr = 256, 2, 6, 1e-3
-    m, g = _setup(cuda, K, gate_type)
-    dirs, poses = _ring_cameras(N)
+    sc = S.parity_scene(K, gate_type=gate_type, device=cuda)
+    m, g = sc.m, sc.g
+    dirs, poses = S.ring_cameras(N, 24)
     gen = torch.Generator().manual_seed(8)
     img = torch.randint(4, (B,), generator=gen)            # images 4 and 5: no pick
     pix = torch.randint(dirs.shape[0], (B,), generator=gen)
@@ -366,7 +332,8 @@ def test_trainer_step_pixels(cuda, gate_type):
 
 def test_trainer_without_pose_arguments_is_unchanged(cuda):
     B, K = 256, 2
-    m, g = _setup(cuda, K, "ray")
+    sc = S.parity_scene(K, device=cuda)
+    m, g = sc.m, sc.g
     tr = Trainer(m, g, B)
     assert not hasattr(tr, "dR") and not hasattr(tr, "dT")
     assert len(tr.grads.params) == 3 and len(tr.opt.param_groups) == 1
@@ -379,7 +346,7 @@ def test_trainer_without_pose_arguments_is_unchanged(cuda):
     with pytest.raises(ValueError, match="directions"):
         tr.step_pixels(torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64), tgt)
     # cameras without refinement: step_pixels runs on batch_rays' rays
-    dirs, poses = _ring_cameras(4)
+    dirs, poses = S.ring_cameras(4, 24)
     tr2 = Trainer(m, g, B, directions=dirs, poses=poses)
     assert not hasattr(tr2, "dR") and len(tr2.grads.params) == 3
     gen = torch.Generator().manual_seed(3)

@@ -23,7 +23,7 @@ from oracle import ml_oracle
 from oracle.ml_oracle import _split_field
 from radnerf_amd import layout as LY
 from radnerf_amd import synthetic as S
-from radnerf_amd.networks import MNGP, NGP, Ray_Gate
+from radnerf_amd.networks import MNGP, NGP
 from radnerf_amd.rendering import ml_render, render
 from parity import check_grads
 
@@ -46,13 +46,13 @@ def _du_unit(h):
     return (h >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
 
 
-def _init(m, K, p=0.5):
+def _init(m, p=0.5):
+    """a single NGP with the tables and occupancy of synthetic.parity_scene"""
     with torch.no_grad():
         m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        bits = S.bitfields(K, m.cascades, p=p)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
+        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(1, LY.FIELD_PARAMS)))
+    bits = S.bitfields(1, m.cascades, p=p)
+    S.set_bitfields(m, bits)
     return bits
 
 
@@ -64,7 +64,7 @@ def test_ngp_render_train_vs_oracle(cuda, fused):
     (rays_a, ts, deltas, ws, rm_samples, vr_samples) vs the oracle too."""
     scale, B = 0.5, 512
     m = NGP(scale, seed=3)
-    bits = _init(m, 1)
+    bits = _init(m)
     m = m.to(cuda)
     o, d = S.rays(B, scale)
     nz = S.noise(1, B)
@@ -111,12 +111,8 @@ def test_ngp_render_train_vs_oracle(cuda, fused):
 @pytest.mark.parametrize("K", [1, 2])
 def test_test_time_render_matches_train_without_jitter(cuda, K):
     scale, B = 0.5, 700
-    m = MNGP(scale, size=K, seed=3)
-    _init(m, K, p=0.3)
-    g = Ray_Gate(K, seed=2)
-    with torch.no_grad():
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-    m, g = m.to(cuda), g.to(cuda)
+    sc = S.parity_scene(K, p=0.3, device=cuda)
+    m, g = sc.m, sc.g
     o, d = (torch.from_numpy(a).to(cuda) for a in S.rays(B, scale))
     with torch.no_grad():
         tr = ml_render(m, g, o, d, d, noise=torch.zeros(K, B, device=cuda), fused=False)
@@ -143,9 +139,7 @@ def test_density_grid_update(cuda):
     sigma) with sigma the oracle's at the replayed point; the bitfield is
     packbits(grid > min(mean, thr)) in Morton byte order."""
     scale, K = 0.5, 2
-    m = MNGP(scale, size=K, seed=3)
-    _init(m, K)
-    m = m.to(cuda)
+    m = S.parity_scene(K, scale=scale, device=cuda).m
     thr = 0.01 * 1024 / 3 ** 0.5                      # train_ml.py:175
     with torch.no_grad():
         for i in range(K):
@@ -182,12 +176,8 @@ def test_test_time_render_vs_oracle(cuda, scale, K, inside):
     the same loop; at scale 16 (exp step 1/256, 6 cascades) it differs from the
     training march, so it is checked against the oracle directly."""
     B = 600
-    m = MNGP(scale, size=K, seed=3)
-    bits = _init(m, K, p=0.3)
-    g = Ray_Gate(K, seed=2)
-    with torch.no_grad():
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-    m, g = m.to(cuda), g.to(cuda)
+    sc = S.parity_scene(K, scale=scale, p=0.3, device=cuda)
+    m, g, bits = sc.m, sc.g, sc.bits
     o, d = S.rays(B, scale)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
     esf = 1 / 256 if scale > 0.5 else 0.0
@@ -219,11 +209,11 @@ def test_image_gate(cuda, scale):
     """gate_type=image (ml_rendering.py:31-36): the gate sees cat(rays_o,
     imgs_d); fused and drop-in chains vs the oracle, outputs and gradients."""
     from radnerf_amd.fused import ml_render_fused
-    from tests_parity_helpers import setup_ml
     dropin = functools.partial(ml_render, fused=False)
     B, K = 384, 2
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = setup_ml(cuda, B, K, scale, gate_type="image")
+    sc = S.parity_scene(K, B, scale=scale, gate_type="image", device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     imgs_d = S.rays(B, scale, seed=77)[1]
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
     outs = []
@@ -364,7 +354,7 @@ def test_density_update_keeps_one_draw_and_its_sigma(cuda, scale, K):
 
 def _ngp_setup(cuda, B, scale=0.5, p=0.5):
     m = NGP(scale, seed=3)
-    bits = _init(m, 1, p=p)
+    bits = _init(m, p=p)
     m = m.to(cuda)
     o, d = S.rays(B, scale)
     return m, bits, o, d
@@ -425,9 +415,9 @@ def test_fused_outputs_without_gradient_raise(cuda):
     chain as values; a loss on them raises at backward instead of silently
     getting no gradient (fused=False differentiates them)."""
     from radnerf_amd.fused import ml_render_fused
-    from tests_parity_helpers import setup_ml
     B, K = 256, 2
-    m, g, o, d, noise, seeds, bits = setup_ml(cuda, B, K, 0.5)
+    sc = S.parity_scene(K, B, scale=0.5, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
     res = ml_render_fused(m, g, to(o), to(d), to(d), noise=to(noise))
     assert res["independent_rgbs"][0].requires_grad

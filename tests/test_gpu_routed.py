@@ -27,7 +27,6 @@ from radnerf_amd import layout as LY
 from radnerf_amd import synthetic as S
 from radnerf_amd.fused import (MAX_SAMPLES, NEAR_DISTANCE, FusedMLRenderer, get_renderer,
                                ml_render_fused)
-from radnerf_amd.networks import MNGP, Ray_Gate
 
 pytestmark = pytest.mark.gpu
 GUARD = 64
@@ -177,18 +176,12 @@ def test_list_march_is_the_dense_march_on_listed_pairs(cuda, B, K, scale):
 
 # ---- the chain ----------------------------------------------------------------------
 def _setup(cuda, B, K, scale, uniform_gate=False):
-    m, g = MNGP(scale, size=K, seed=3), Ray_Gate(K, seed=2)
-    with torch.no_grad():
-        m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=GATE_SEED)[0]))
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    with torch.no_grad():                               # this file's gate on the shared scene
+        sc.g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=GATE_SEED)[0]))
         if uniform_gate:
-            g.params[LY.gate_params(0):].zero_()        # the last layer: every logit 0
-        bits = S.bitfields(K, m.cascades, p=0.5)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = S.rays(B, scale)
-    return m.to(cuda), g.to(cuda), o, d, S.noise(K, B), S.loss_seeds(B, K), bits
+            sc.g.params[LY.gate_params(0):].zero_()     # the last layer: every logit 0
+    return sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
 
 
 def _bg(scale, cuda):

@@ -6,11 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-from radnerf_amd import layout as LY
 from radnerf_amd import synthetic as S
 from radnerf_amd.fused import get_renderer, ml_render_fused
 from radnerf_amd.losses import NeRFLoss, fused_nerf_loss
-from radnerf_amd.networks import MNGP, Ray_Gate
 from radnerf_amd.optim import FusedAdam
 
 pytestmark = pytest.mark.gpu
@@ -80,26 +78,14 @@ def test_fused_adam_matches_torch_adam(cuda, betas):
     assert torch.allclose(st["exp_avg_sq"].cpu(), st_ref["exp_avg_sq"], rtol=1e-5, atol=1e-12)
 
 
-def _setup(cuda, B, K, scale=0.5):
-    m = MNGP(scale, size=K, seed=3)
-    g = Ray_Gate(K, seed=2)
-    with torch.no_grad():
-        m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        bits = S.bitfields(K, m.cascades, p=0.5)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    return m.to(cuda), g.to(cuda)
-
-
 @pytest.mark.parametrize("B,K,scale", [(512, 2, 0.5), (512, 4, 16.0), (72, 9, 0.5)])
 def test_fused_train_step_matches_autograd(cuda, B, K, scale):
     """(512, 4, 16): config C4's branch -- K = 4 with depth-mutual, exp step
     1/256, 6 cascades, black background (scripts/rad_360v2.sh:3-7).
     (72, 9, 0.5): above 8 sub-NeRFs, the per-model field kernels."""
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g = _setup(cuda, B, K, scale)
+    sc = S.parity_scene(K, scale=scale, device=cuda)
+    m, g = sc.m, sc.g
     o, d = (torch.from_numpy(a).to(cuda) for a in S.rays(B, scale))
     nz = torch.from_numpy(S.noise(K, B)).to(cuda)
     tgt = torch.rand(B, 3, generator=torch.Generator().manual_seed(5)).to(cuda)
@@ -125,7 +111,8 @@ def test_adam_refreshes_derived_caches(cuda):
     """After an in-place kernel update the f16 table mirror is current and the
     MLP fragments are repacked (no stale weights in the next forward)."""
     B, K = 256, 2
-    m, g = _setup(cuda, B, K)
+    sc = S.parity_scene(K, device=cuda)
+    m, g = sc.m, sc.g
     o, d = (torch.from_numpy(a).to(cuda) for a in S.rays(B, 0.5))
     nz = torch.from_numpy(S.noise(K, B)).to(cuda)
     ml_render_fused(m, g, o, d, d, noise=nz)                    # builds the caches

@@ -23,7 +23,6 @@ from radnerf_amd._lib import lib, use_ablation_build  # noqa: E402
 
 use_ablation_build()        # rn_set_debug_flags switches live only in librn_abl.so
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def main():
@@ -33,20 +32,9 @@ def main():
     B = int(os.environ.get("ABL_RAYS", 8192))
     K = int(os.environ.get("ABL_K", 2))
     scale = float(os.environ.get("ABL_SCALE", 0.5))
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale))
-    nz = torch.from_numpy(S.noise(K, B)).to(dev)
-    sd = [torch.from_numpy(a).to(dev) for a in S.loss_seeds(B, K)]
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, sd, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bg, sc.esf
+    gg, mg, ag = sc.grid_grad, sc.mlp_grad, sc.gate_grad
     rens = {}
     for key in ("", "a"):          # "a": the int32 atomic scatter (own workspace and scales)
         rr = FusedMLRenderer(m, g, B)

@@ -32,18 +32,18 @@ usage: python tools/checkpoint_step.py [c3] [c5] [--steps N] [--every N] [--dir 
        (FILE, appended to: profiles/checkpoint/checkpoint_step.jsonl)
        python tools/checkpoint_step.py --ab PARENT_TREE [--ab-out FILE]
 """
-import json
 import math
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
+
+from steptime import ab_main, append_jsonl  # noqa: E402
 
 SHAPES = {"c3": (2, 8192, 0.5), "c5": (8, 8192, 16.0)}
 SEG = 10
@@ -72,15 +72,10 @@ def cameras(scale):
 def make_trainer(name, dev):
     import torch
     from radnerf_amd import synthetic as S
-    from radnerf_amd.networks import MNGP, Ray_Gate
     from radnerf_amd.trainer import Trainer
     K, B, scale = SHAPES[name]
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g = sc.m, sc.g
     dirs, poses = cameras(scale)
     u8 = torch.randint(0, 256, (N_IMG, RES * RES, 3), dtype=torch.uint8,
                        generator=torch.Generator().manual_seed(7))
@@ -147,44 +142,6 @@ def run(name, steps, every, where):
     return out
 
 
-AB_SHAPES = {"c3": ["--steps", "40", "--warmup", "5"],
-             "c5": ["--steps", "20", "--warmup", "3", "--models", "8", "--scale", "16",
-                    "--rays", "8192"]}
-
-
-def ab_default(parent, dest, rounds=3):
-    """bench.py of this tree and of `parent`, alternating, each run a child
-    process of its own (this process never touches the GPU)."""
-    trees = {"new": ROOT, "old": os.path.abspath(parent)}
-    vals = {(c, v): [] for c in AB_SHAPES for v in trees}
-    for _ in range(rounds):
-        for v, tree in trees.items():
-            for c, extra in AB_SHAPES.items():
-                res = subprocess.run([sys.executable, os.path.join(tree, "bench.py"), "--gpus", "1"]
-                                     + extra, capture_output=True, text=True, timeout=300)
-                if res.returncode != 0:
-                    raise SystemExit(f"bench.py ({v}, {c}) failed: {res.stderr[-2000:]}")
-                d = json.loads(res.stdout.strip().splitlines()[-1])
-                vals[(c, v)].append((d["value"], d["ms_per_step"]))
-                print(f"{c} {v}: {d['value']:.2f}", file=sys.stderr, flush=True)
-    lines = ["# the default step, bench.py --gpus 1 --steps 40 --warmup 5 "
-             "(C5: --steps 20 --warmup 3),",
-             "# the parent commit's tree with its own library (old) and this tree (new),",
-             "# alternating new / old per round in one job on one MI355X; M samples/s fwd+bwd, "
-             "ms per step",
-             "# C3: defaults (K 2, 8192 rays, scale 0.5); C5: --models 8 --scale 16 --rays 8192",
-             "# (no file under csrc/ or include/ differs between the two trees)"]
-    for c in AB_SHAPES:
-        for v in ("old", "new"):
-            xs = [a for a, _ in vals[(c, v)]]
-            lines.append(f"{c} {v}: " + "  ".join(f"{a:.2f} ({b:.4f} ms)" for a, b in vals[(c, v)])
-                         + f"  median {np.median(xs):.2f}  spread {min(xs):.2f}-{max(xs):.2f}")
-    os.makedirs(os.path.dirname(os.path.abspath(dest)), exist_ok=True)
-    with open(dest, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines), flush=True)
-
-
 def _opt(args, flag, default, kind=str):
     if flag in args:
         i = args.index(flag)
@@ -197,23 +154,17 @@ def _opt(args, flag, default, kind=str):
 if __name__ == "__main__":
     args = sys.argv[1:]
     if "--ab" in args:
-        parent = _opt(args, "--ab", None)
-        ab_default(parent, _opt(args, "--ab-out", os.path.join(ROOT, "profiles", "checkpoint",
-                                                              "ab_default.txt")))
+        ab_main(args, os.path.join(ROOT, "profiles", "checkpoint", "ab_default.txt"))
         sys.exit(0)
     dest = _opt(args, "--out",
                 os.path.join(ROOT, "profiles", "checkpoint", "checkpoint_step.jsonl"))
     steps, every = _opt(args, "--steps", 300, int), _opt(args, "--every", 100, int)
     where = _opt(args, "--dir", None)
-    os.makedirs(os.path.dirname(os.path.abspath(dest)), exist_ok=True)
     import torch
     tmp = where or tempfile.mkdtemp()
     try:
         for name in args or ["c3", "c5"]:
-            line = json.dumps(run(name, steps, every, tmp))
-            print(line, flush=True)
-            with open(dest, "a") as f:
-                f.write(line + "\n")
+            append_jsonl(dest, run(name, steps, every, tmp))
             torch.cuda.empty_cache()
     finally:
         if where is None:

@@ -34,16 +34,11 @@ usage: python tools/deterministic_step.py [c3] [c5] [--out FILE]
        (FILE, appended to: profiles/deterministic/deterministic_step.jsonl)
        python tools/deterministic_step.py --ab PARENT_TREE [--ab-out FILE]
 """
-import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -51,7 +46,7 @@ from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import lib  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
 from radnerf_amd.losses import fused_nerf_loss  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from steptime import ab_main, alone_ms, append_jsonl, interleaved_ms  # noqa: E402
 
 SHAPES = {"c3": (2, 8192, 0.5), "c5": (8, 8192, 16.0)}
 LAMBDAS = dict(lambda_cv_importance=1e-2, lambda_depth_mutual=1e-3)
@@ -67,20 +62,10 @@ def _median(x):
 def run(name, steps=10, rounds=6):
     K, B, scale = SHAPES[name]
     dev = torch.device("cuda")
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale, seed=0))
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg, sc.esf
+    gg, mg, ag = sc.grid_grad, sc.mlp_grad, sc.gate_grad
     target = torch.rand(B, 3, generator=torch.Generator().manual_seed(7)).to(dev)
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
     rs = {"default": FusedMLRenderer(m, g, B), "intgrad": FusedMLRenderer(m, g, B),
           "det": FusedMLRenderer(m, g, B, deterministic=True)}
     rs["intgrad"].int_grad = True
@@ -89,17 +74,7 @@ def run(name, steps=10, rounds=6):
         r.train_step(o, d, d, target, nz, bg, exp_step_factor=esf, grid_grad=gg, mlp_grad=mg,
                      gate_grad=ag, **LAMBDAS)
 
-    times = {k: [] for k in rs}
-    for rnd in range(rounds):
-        for k, r in rs.items():
-            step(r)                                 # warm-up of this form
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                step(r)
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms({k: (lambda r=r: step(r)) for k, r in rs.items()}, steps, rounds)
     out = {"shape": name, "K": K, "rays": B, "scale": scale,
            "samples": rs["det"].ws.n_samples(), "steps": steps, "rounds": rounds - 1,
            "scatter_mode": {k: r.scatter_mode for k, r in rs.items()},
@@ -107,8 +82,7 @@ def run(name, steps=10, rounds=6):
            "dw_part_bytes": rs["det"].ws.dw_part.numel() * 4,
            "gate_part_bytes": 0 if K == 1 else rs["det"].ws.gate_part.numel() * 4}
     for k, t in times.items():
-        out[k + "_ms"] = _median(t)
-        out[k + "_spread_ms"] = [round(float(min(t)), 4), round(float(max(t)), 4)]
+        out[k + "_ms"], out[k + "_spread_ms"] = t["ms"], t["range_ms"]
     # the launches' own times (events around each, so the step itself is slower)
     for k in ("default", "det"):
         r = rs[k]
@@ -137,90 +111,20 @@ def run(name, steps=10, rounds=6):
         alone["gate_reduce"] = lambda: L.reduce_partials(
             w.gate_part.data_ptr(), w.gate_part.shape[0], w.gate_part.shape[1], ag.data_ptr(), st)
         alone["gate_colsum"] = lambda: L.colsum_ordered(gate.data_ptr(), B, K, imp.data_ptr(), st)
-    out["alone_ms"] = {}
-    for k, fn in alone.items():
-        ts = []
-        for _ in range(steps + 2):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            ts.append(a.elapsed_time(b))
-        out["alone_ms"][k] = _median(ts[2:])
+    out["alone_ms"] = {k: alone_ms(fn, steps, 2) for k, fn in alone.items()}
     return out
-
-
-AB_SHAPES = {"c3": ["--steps", "40", "--warmup", "5"],
-             "c5": ["--steps", "20", "--warmup", "3", "--models", "8", "--scale", "16",
-                    "--rays", "8192"]}
-
-
-def ab_default(parent, dest, rounds=3):
-    """bench.py of this tree and of `parent`, alternating, each run a child
-    process of its own (this process never touches the GPU)."""
-    trees = {"new": ROOT, "old": os.path.abspath(parent)}
-    vals = {(c, v): [] for c in AB_SHAPES for v in trees}
-    for _ in range(rounds):
-        for v, tree in trees.items():
-            for c, extra in AB_SHAPES.items():
-                res = subprocess.run([sys.executable, os.path.join(tree, "bench.py"), "--gpus", "1"]
-                                     + extra, capture_output=True, text=True, timeout=300)
-                if res.returncode != 0:
-                    raise SystemExit(f"bench.py ({v}, {c}) failed: {res.stderr[-2000:]}")
-                d = json.loads(res.stdout.strip().splitlines()[-1])
-                vals[(c, v)].append((d["value"], d["ms_per_step"]))
-    lines = ["# default step (deterministic off), bench.py --gpus 1 --steps 40 --warmup 5 "
-             "(C5: --steps 20 --warmup 3),",
-             "# the parent commit's tree with its own library (old) and this tree (new),",
-             "# alternating new / old per round in one job on one MI355X; M samples/s fwd+bwd, "
-             "ms per step",
-             "# C3: defaults (K 2, 8192 rays, scale 0.5); C5: --models 8 --scale 16 --rays 8192"]
-    for c in AB_SHAPES:
-        for v in ("old", "new"):
-            xs = [a for a, _ in vals[(c, v)]]
-            lines.append(f"{c} {v}: " + "  ".join(f"{a:.2f} ({b:.4f} ms)" for a, b in vals[(c, v)])
-                         + f"  median {np.median(xs):.2f}  spread {min(xs):.2f}-{max(xs):.2f}")
-    tmp = tempfile.mkdtemp()
-    try:
-        for v, tree in trees.items():
-            subprocess.run([sys.executable, os.path.join(tree, "bench.py"), "--gpus", "1",
-                            "--steps", "5", "--warmup", "2", "--dump-outputs",
-                            os.path.join(tmp, v)], capture_output=True, check=True, timeout=300)
-        eq = {n[:-4]: bool(np.array_equal(np.load(os.path.join(tmp, "new", n)),
-                                          np.load(os.path.join(tmp, "old", n))))
-              for n in sorted(os.listdir(os.path.join(tmp, "new")))}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    lines.append("# --dump-outputs of one more C3 run each, bitwise equal old vs new (mlp_grad and "
-                 "gate_grad are fp32")
-    lines.append("# atomics in arrival order, which differ between any two default runs): "
-                 + ", ".join(f"{k} {'yes' if e else 'no'}" for k, e in eq.items()))
-    os.makedirs(os.path.dirname(os.path.abspath(dest)), exist_ok=True)
-    with open(dest, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines), flush=True)
 
 
 if __name__ == "__main__":
     args = sys.argv[1:]
     if "--ab" in args:
-        i = args.index("--ab")
-        parent = args[i + 1]
-        dest = os.path.join(ROOT, "profiles", "deterministic", "ab_default.txt")
-        if "--ab-out" in args:
-            dest = args[args.index("--ab-out") + 1]
-        ab_default(parent, dest)
+        ab_main(args, os.path.join(ROOT, "profiles", "deterministic", "ab_default.txt"))
         sys.exit(0)
     dest = os.path.join(ROOT, "profiles", "deterministic", "deterministic_step.jsonl")
     if "--out" in args:
         i = args.index("--out")
         dest = args[i + 1]
         del args[i:i + 2]
-    os.makedirs(os.path.dirname(os.path.abspath(dest)), exist_ok=True)
     for name in args or ["c3", "c5"]:
-        line = json.dumps(run(name))
-        print(line, flush=True)
-        with open(dest, "a") as f:
-            f.write(line + "\n")
+        append_jsonl(dest, run(name))
         torch.cuda.empty_cache()

@@ -20,8 +20,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "te
 from oracle import field_oracle as fo  # noqa: E402
 from oracle import ml_oracle  # noqa: E402
 from radnerf_amd import layout as LY  # noqa: E402
+from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import get_renderer, ml_render_fused  # noqa: E402
-from test_gpu_ml import LAYERS, _run, _setup  # noqa: E402
+from test_gpu_ml import LAYERS, _run  # noqa: E402
 
 
 def rel(a, b):
@@ -31,7 +32,8 @@ def rel(a, b):
 def main(scale, K, B):
     cuda = torch.device("cuda:0")
     esf = 1 / 256 if scale > 0.5 else 0.0
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, scale=scale, K=K)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     rf, gf = _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, esf)
     w = get_renderer(m, g, B).ws
     gm = m.xyz_encoder.params.detach().cpu().view(-1, 2)

@@ -19,17 +19,15 @@ usage: python tools/distortion_step.py [c3] [c5]
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd")]
-import numpy as np  # noqa: E402
+sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
 import torch  # noqa: E402
 
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import lib  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from steptime import interleaved_ms  # noqa: E402
 
 SHAPES = {"c3": (2, 8192, 0.5), "c5": (8, 8192, 16.0)}
 LAMBDA = 1e-3       # --distortion_loss_w of the reference's 360 scripts
@@ -78,22 +76,11 @@ class Explicit:
 def run(name, steps=10, rounds=6):
     K, B, scale = SHAPES[name]
     dev = torch.device("cuda")
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale, seed=0))
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
-    sd = [torch.from_numpy(a).to(dev) for a in S.loss_seeds(B, K, seed=4)]
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, sd, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bg, sc.esf
     r = FusedMLRenderer(m, g, B)
     ex = Explicit(r)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
+    gg, mg, ag = sc.grid_grad, sc.mlp_grad, sc.gate_grad
     L = lib()
     plain_bw = L.ml_composite_bw
 
@@ -116,23 +103,12 @@ def run(name, steps=10, rounds=6):
             L.ml_composite_bw = plain_bw
 
     forms = {"default": default, "inchain": inchain, "explicit": explicit}
-    times = {k: [] for k in forms}
-    for rnd in range(rounds):
-        for k, fn in forms.items():
-            fn()                                    # warm-up of this form
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms(forms, steps, rounds)
     out = {"shape": name, "K": K, "rays": B, "scale": scale, "samples": r.ws.n_samples(),
            "steps": steps, "rounds": rounds - 1, "lambda": LAMBDA,
            "extra_bytes_explicit": 3 * 4 * r.ws.capacity}
     for k, t in times.items():
-        out[k + "_ms"] = round(float(np.median(t)), 4)
-        out[k + "_spread_ms"] = [round(float(min(t)), 4), round(float(max(t)), 4)]
+        out[k + "_ms"], out[k + "_spread_ms"] = t["ms"], t["range_ms"]
     print(json.dumps(out), flush=True)
 
 

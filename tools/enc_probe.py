@@ -16,7 +16,6 @@ import torch  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import lib  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def main():
@@ -26,16 +25,8 @@ def main():
     scale = float(os.environ.get("ABL_SCALE", 0.5))
     blocks = [int(x) for x in (os.environ.get("ENC_BLOCKS", "4096").split(","))]
     mblocks = [int(x) for x in (os.environ.get("MLP_BLOCKS", "1024").split(","))]
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale))
-    nz = torch.from_numpy(S.noise(K, B)).to(dev)
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg, sc.esf
     r = FusedMLRenderer(m, g, B)
     r.forward(o, d, d, nz, bg, 1e-4, esf)
     L = lib()

@@ -12,21 +12,13 @@ import torch  # noqa: E402
 
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def main():
     dev = torch.device("cuda")
     B, K = 8192, 2
-    m = MNGP(0.5, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, 1, p=0.5)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B))
-    nz = torch.from_numpy(S.noise(K, B)).to(dev)
-    bg = torch.ones(3, device=dev)
+    sc = S.bench_scene(K, B, 0.5, dev)
+    m, g, o, d, nz, bg = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg
     r = FusedMLRenderer(m, g, B)
     r.forward(o, d, d, nz, bg)
     st = torch.cuda.current_stream().cuda_stream

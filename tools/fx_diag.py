@@ -13,23 +13,15 @@ from radnerf_amd import layout as LY  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import lib  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def main():
     B, K, scale = int(sys.argv[1]) if len(sys.argv) > 1 else 8192, 2, 0.5
     # usage: fx_diag.py [B] [steps] [adam]
     dev = torch.device("cuda", 0)
-    model = MNGP(scale, size=K, seed=3).to(dev)
-    gate = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, model.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(model, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale, seed=0))
-    noise = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
-    g_rgb, g_op, g_depth = (torch.from_numpy(s).to(dev) for s in S.loss_seeds(B, K, seed=4))
-    bg = torch.ones(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    model, gate, o, d, noise, bg = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg
+    g_rgb, g_op, g_depth = sc.seeds
     r = FusedMLRenderer(model, gate, B)
     L = lib()
     orig = L.grid_fx_fold

@@ -16,8 +16,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from radnerf_amd import layout as LY  # noqa: E402
+from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import get_renderer, ml_render_fused  # noqa: E402
-from test_gpu_ml import _run, _setup  # noqa: E402
+from test_gpu_ml import _run  # noqa: E402
 
 
 def main():
@@ -26,7 +27,8 @@ def main():
     scale = float(sys.argv[3]) if len(sys.argv) > 3 else 16.0
     esf = 1 / 256 if scale > 0.5 else 0.0
     cuda = torch.device("cuda")
-    m, g, o, d, noise, seeds, bits = _setup(cuda, B=B, K=K, scale=scale)
+    sc = S.parity_scene(K, B, scale=scale, device=cuda)
+    m, g, o, d, noise, seeds, bits = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bits
     r = get_renderer(m, g, B)
     lv = LY.grid_levels(scale)
     _run(ml_render_fused, m, g, o, d, noise, seeds, cuda, esf)

@@ -28,7 +28,6 @@ from radnerf_amd import layout as LY  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import LIB_PATH  # noqa: E402
 from radnerf_amd.fused import get_renderer, ml_render_fused  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 from radnerf_amd.optim import FusedAdam  # noqa: E402
 
 
@@ -39,16 +38,8 @@ def main():
     scale = 0.5
     f32_levels = [int(x) for x in os.environ.get("FX_F32_LEVELS", "").split(",") if x]
     cuda = torch.device("cuda")
-    m = MNGP(scale, size=K, seed=3)
-    g = Ray_Gate(K, seed=2)
-    with torch.no_grad():
-        m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
-        m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        g.params.copy_(torch.from_numpy(S.mlp_params(1, LY.gate_params(K), seed=6)[0]))
-        bits = S.bitfields(K, m.cascades, p=0.5)
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    m, g = m.to(cuda), g.to(cuda)
+    sc = S.parity_scene(K, scale=scale, device=cuda)
+    m, g = sc.m, sc.g
     r = get_renderer(m, g, B)
     lv = LY.grid_levels(scale)
 

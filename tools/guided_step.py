@@ -22,11 +22,11 @@ conv   tools/train_demo.py's analytic sphere as a training set (32 images of
 
 usage: python tools/guided_step.py [time] [conv] [--out DIR]
 """
+import functools
 import json
 import math
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
@@ -36,13 +36,10 @@ import torch  # noqa: E402
 from radnerf_amd import sampler  # noqa: E402
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 from radnerf_amd.trainer import Trainer  # noqa: E402
+from steptime import alone_ms, append_jsonl, interleaved_ms  # noqa: E402
 from train_demo import R_SPHERE, batch  # noqa: E402
 
 DEV = torch.device("cuda")
-
-
-def _median(x):
-    return round(float(np.median(x)), 4)
 
 
 def cameras(n_img, W, H, half=0.3, seed=0):
@@ -88,16 +85,7 @@ def _trainer(data, wh, B, seed, **kw):
 
 
 # ---------------------------------------------------------------- step time
-def _alone(fn, n=30):
-    ts = []
-    for _ in range(n + 3):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b))
-    return _median(ts[3:])
+_alone = functools.partial(alone_ms, n=30, skip=3)
 
 
 def step_time(steps=16, rounds=8):
@@ -118,24 +106,14 @@ def step_time(steps=16, rounds=8):
         s.emap[hot] = 300.0
         s.update_weights()
     one_cell_map(gs)
-    times = {k: [] for k in trs}
-    for rnd in range(rounds):
-        for k, tr in trs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                tr.step_sampled()
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms({k: tr.step_sampled for k, tr in trs.items()}, steps, rounds, warm=False)
     b = trs["one_cell"].last_batch
     in_hot = float((b["cell_idx"] == hot).float().mean())
     out = {"what": "step_sampled", "images": n_img, "wh": [W, H], "rays": B, "K": 2, "scale": 0.5,
            "n_cells": gs.n_cells, "steps_per_round": steps, "rounds": rounds - 1,
            "one_cell_share_of_batch": round(in_hot, 4)}
     for k, t in times.items():
-        out[k + "_ms"] = _median(t)
-        out[k + "_spread_ms"] = [round(float(min(t)), 4), round(float(max(t)), 4)]
+        out[k + "_ms"], out[k + "_spread_ms"] = t["ms"], t["range_ms"]
     # the four kernels alone, on a flat and on the one-cell map
     tr = trs["guided"]
     s, K = tr.guided, tr.model.size
@@ -216,12 +194,8 @@ if __name__ == "__main__":
         i = args.index("--out")
         dest = args[i + 1]
         del args[i:i + 2]
-    os.makedirs(dest, exist_ok=True)
     for name in args or ["time", "conv"]:
-        res = {"time": step_time, "conv": convergence}[name]()
-        line = json.dumps(res)
-        print(line, flush=True)
-        with open(os.path.join(dest, {"time": "guided_step.jsonl",
-                                      "conv": "guided_convergence.jsonl"}[name]), "a") as f:
-            f.write(line + "\n")
+        append_jsonl(os.path.join(dest, {"time": "guided_step.jsonl",
+                                         "conv": "guided_convergence.jsonl"}[name]),
+                     {"time": step_time, "conv": convergence}[name]())
         torch.cuda.empty_cache()

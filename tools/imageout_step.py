@@ -18,12 +18,12 @@ The split of the two saving forms (the map kernels between events, the copies,
 zlib and the file write timed on their own) is in the same line.
 
   --validate-only   time `plain` alone: with --tree DIR on the package of
-                    another tree (an A/B against an older checkout)
+                    another tree (an A/B against an older checkout, no
+                    older than synthetic.set_bitfields)
 
 usage: python tools/imageout_step.py [--out FILE] [--res N] [--images N]
                                      [--validate-only] [--tree DIR]
 """
-import json
 import os
 import shutil
 import sys
@@ -34,15 +34,17 @@ import zlib
 _argv = sys.argv[1:]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TREE = os.path.abspath(_argv[_argv.index("--tree") + 1]) if "--tree" in _argv else ROOT
-sys.path[:0] = [TREE, os.path.join(TREE, "rad-nerf_amd"), os.path.join(TREE, "tools")]
+sys.path[:0] = [TREE, os.path.join(TREE, "rad-nerf_amd"), os.path.join(TREE, "tools"),
+                os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pose_demo import ring_cameras  # noqa: E402
 from radnerf_amd import layout as LY  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras  # noqa: E402
 from radnerf_amd.trainer import Trainer  # noqa: E402
+from steptime import append_jsonl, interleaved_ms  # noqa: E402
 
 
 def setup(res, n_img):
@@ -50,12 +52,10 @@ def setup(res, n_img):
     dev = torch.device("cuda")
     m = MNGP(scale, size=K, seed=3)
     g = Ray_Gate(K, seed=4)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
+    S.set_bitfields(m, S.bitfields(K, m.cascades, p=0.5, seed=1))
     with torch.no_grad():
         m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
     m, g = m.to(dev), g.to(dev)
     dirs, poses = (t.to(dev) for t in ring_cameras(n_img, res))
     gt = torch.rand(n_img, dirs.shape[0], 3, generator=torch.Generator().manual_seed(0)).to(dev)
@@ -65,19 +65,10 @@ def setup(res, n_img):
 
 def timed(forms, n_img, rounds=6):
     """median ms per image of each form, the forms alternating per round"""
-    times = {k: [] for k in forms}
-    for rnd in range(rounds):
-        for k, fn in forms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / n_img * 1e3)
     out = {}
-    for k, t in times.items():
-        out[k + "_ms"] = round(float(np.median(t)), 4)
-        out[k + "_spread_ms"] = [round(float(min(t)), 4), round(float(max(t)), 4)]
+    for k, t in interleaved_ms(forms, 1, rounds, warm=False).items():
+        out[k + "_ms"] = round(t["ms"] / n_img, 4)
+        out[k + "_spread_ms"] = [round(x / n_img, 4) for x in t["range_ms"]]
     return out
 
 
@@ -211,9 +202,5 @@ if __name__ == "__main__":
     opt = lambda name, default: type(default)(_argv[_argv.index(name) + 1]) \
         if name in _argv else default
     path = opt("--out", os.path.join(ROOT, "profiles", "imageout", "imageout_step.jsonl"))
-    line = json.dumps(run(res=opt("--res", 800), n_img=opt("--images", 4),
-                          validate_only="--validate-only" in _argv))
-    print(line, flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "a") as f:
-        f.write(line + "\n")
+    append_jsonl(path, run(res=opt("--res", 800), n_img=opt("--images", 4),
+                           validate_only="--validate-only" in _argv))

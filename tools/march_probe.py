@@ -16,21 +16,13 @@ from radnerf_amd._lib import lib, use_ablation_build  # noqa: E402
 
 use_ablation_build()        # rn_set_debug_flags switches live only in librn_abl.so
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def main():
     K, scale, B = int(sys.argv[1]), float(sys.argv[2]), int(sys.argv[3])
     dev = torch.device("cuda")
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale))
-    nz = torch.from_numpy(S.noise(K, B)).to(dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.esf
     bg = torch.zeros(3, device=dev)
     r = FusedMLRenderer(m, g, B)
     r.trace = {"march"}

@@ -16,30 +16,19 @@ import torch  # noqa: E402
 
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def main():
     dev = torch.device("cuda")
     B, K = 8192, 2
-    m = MNGP(0.5, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, 1, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, 0.5, seed=0))
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
-    sd = [torch.from_numpy(a).to(dev) for a in S.loss_seeds(B, K, seed=4)]
-    bg = torch.ones(3, device=dev)
+    sc = S.bench_scene(K, B, 0.5, dev)
+    m, g, o, d, nz, sd, bg = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bg
     h = B // 2
     halves = [(o[:h].contiguous(), d[:h].contiguous(), nz[:, :h].contiguous(), [x[:h].contiguous() for x in sd]),
               (o[h:].contiguous(), d[h:].contiguous(), nz[:, h:].contiguous(), [x[h:].contiguous() for x in sd])]
     rs = [FusedMLRenderer(m, g, h), FusedMLRenderer(m, g, h)]
     full = FusedMLRenderer(m, g, B)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
+    gg, mg, ag = sc.grid_grad, sc.mlp_grad, sc.gate_grad
     s1 = torch.cuda.current_stream()
     s2 = torch.cuda.Stream()
 

@@ -16,7 +16,6 @@ import torch  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import lib  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def pack(pairs):
@@ -31,16 +30,8 @@ def main():
     B = int(os.environ.get("ABL_RAYS", 8192))
     K = int(os.environ.get("ABL_K", 2))
     scale = float(os.environ.get("ABL_SCALE", 0.5))
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale))
-    nz = torch.from_numpy(S.noise(K, B)).to(dev)
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg, sc.esf
     r = FusedMLRenderer(m, g, B)
     r.forward(o, d, d, nz, bg, 1e-4, esf)
     torch.cuda.synchronize()

@@ -32,27 +32,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "to
 import torch  # noqa: E402
 
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras  # noqa: E402
 from radnerf_amd.trainer import Trainer  # noqa: E402
 from train_demo import R_SPHERE  # noqa: E402
-
-
-def ring_cameras(n_img, res, radius=1.5, half=0.3):
-    """n_img cameras on a ring around the origin, looking at it (c2w columns
-    right / up / forward): unit pixel directions (res * res, 3) of half-width
-    `half` at unit depth, and poses (n_img, 3, 4)."""
-    u = torch.linspace(-half, half, res)
-    y, x = torch.meshgrid(u, u, indexing="ij")
-    dirs = torch.stack([x.reshape(-1), y.reshape(-1), torch.ones(res * res)], -1)
-    dirs = dirs / dirs.norm(dim=1, keepdim=True)
-    ang = torch.arange(n_img) * (2 * math.pi / n_img) + 0.3
-    pos = torch.stack([radius * torch.cos(ang), radius * torch.sin(ang),
-                       0.4 * torch.sin(3 * ang)], -1)
-    fwd = -pos / pos.norm(dim=1, keepdim=True)
-    right = torch.linalg.cross(fwd, torch.tensor([0.0, 0.0, 1.0]).expand_as(fwd))
-    right = right / right.norm(dim=1, keepdim=True)
-    up = torch.linalg.cross(right, fwd)
-    poses = torch.cat([torch.stack([right, up, fwd], 2), pos[:, :, None]], 2)
-    return dirs.contiguous(), poses.contiguous()
 
 
 def rodrigues(v):

@@ -23,23 +23,21 @@ its cost grows with N.
 
 usage: python tools/pose_step.py [--out FILE]
 """
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pose_demo import ring_cameras  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd._lib import lib  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer, ml_render_fused  # noqa: E402
 from radnerf_amd.losses import NeRFLoss  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 from radnerf_amd.rays import batch_rays, pose_rays, pose_rays_backward  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras  # noqa: E402
+from steptime import append_jsonl, interleaved_ms  # noqa: E402
 
 LAMBDAS = dict(lambda_opacity=1e-3, lambda_cv_importance=1e-2)
 
@@ -87,12 +85,8 @@ def kernel_us(fn, reps=15, burst=20):
 def run(steps=10, rounds=6, n_img=100, res=400):
     K, B, scale = 2, 8192, 0.5
     dev = torch.device("cuda")
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, nz, bg = sc.m, sc.g, sc.noise, sc.bg
     dirs, poses = (t.to(dev) for t in ring_cameras(n_img, res))
     gen = torch.Generator().manual_seed(0)
     img = torch.randint(n_img, (B,), generator=gen).to(dev)
@@ -100,15 +94,10 @@ def run(steps=10, rounds=6, n_img=100, res=400):
     tgt = torch.rand(B, 3, generator=gen).to(dev)
     dR = (1e-2 * torch.randn(n_img, 3, generator=gen)).to(dev)
     dT = (1e-2 * torch.randn(n_img, 3, generator=gen)).to(dev)
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
-    bg = torch.ones(3, device=dev)
     mean = dirs.mean(0).contiguous()
     r = FusedMLRenderer(m, g, B)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
     oR, oT = torch.empty_like(dR), torch.empty_like(dT)
-    kw = dict(grid_grad=gg, mlp_grad=mg, gate_grad=ag, **LAMBDAS)
+    kw = dict(grid_grad=sc.grid_grad, mlp_grad=sc.mlp_grad, gate_grad=sc.gate_grad, **LAMBDAS)
     loss_fn = NeRFLoss()
     leaves = [dR.clone().requires_grad_(True), dT.clone().requires_grad_(True)]
 
@@ -134,23 +123,12 @@ def run(steps=10, rounds=6, n_img=100, res=400):
         sum(v.mean() for v in loss_fn(res, {"rgb": tgt}, **LAMBDAS).values()).backward()
 
     forms = {"default": default, "raygrad": raygrad, "fused": fused, "torch": composed}
-    times = {k: [] for k in forms}
-    for rnd in range(rounds):
-        for k, fn in forms.items():
-            fn()                                    # warm-up of this form
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms(forms, steps, rounds)
     out = {"shape": "c3", "K": K, "rays": B, "scale": scale, "images": n_img,
            "pixels_per_image": res * res, "samples": r.ws.n_samples(), "steps": steps,
            "rounds": rounds - 1}
     for k, t in times.items():
-        out[k + "_ms"] = round(float(np.median(t)), 4)
-        out[k + "_spread_ms"] = [round(float(min(t)), 4), round(float(max(t)), 4)]
+        out[k + "_ms"], out[k + "_spread_ms"] = t["ms"], t["range_ms"]
     # the fused and the composed step agree on what they compute
     fused()
     composed()
@@ -181,8 +159,4 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     path = argv[argv.index("--out") + 1] if "--out" in argv else \
         os.path.join(ROOT, "profiles", "pose", "pose_step.jsonl")
-    line = json.dumps(run())
-    print(line, flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "a") as f:
-        f.write(line + "\n")
+    append_jsonl(path, run())

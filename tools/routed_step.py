@@ -19,8 +19,8 @@ arbitrary; the fractions say how the work was shared out.
 Shapes: C3 (K = 2, 8192 rays, scale 0.5) and C5's per-GPU shape (K = 8, 8192
 rays, scale 16, exp step 1/256).
 
-With --ab PARENT_TREE it runs the default-path A/B of
-tools/deterministic_step.py instead (bench.py of this tree and of a checkout
+With --ab PARENT_TREE it runs the default-path A/B of tools/steptime.py
+instead (bench.py of this tree and of a checkout
 of the parent commit with its own library, alternating per round) into
 profiles/routed/ab_default.txt (--ab-out FILE).
 
@@ -28,19 +28,16 @@ usage: python tools/routed_step.py [c3] [c5] [--out FILE]
        (FILE, appended to: profiles/routed/routed_step.jsonl)
        python tools/routed_step.py --ab PARENT_TREE [--ab-out FILE] [--ab-rounds N]
 """
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from steptime import ab_main, append_jsonl, interleaved_ms  # noqa: E402
 
 SHAPES = {"c3": (2, 8192, 0.5), "c5": (8, 8192, 16.0)}
 LAMBDAS = dict(lambda_cv_importance=1e-2, lambda_depth_mutual=1e-3)
@@ -50,20 +47,10 @@ LEGS = {"dense": {}, "all_live": {}, "top2": dict(gate_topk=2), "top1": dict(gat
 def run(name, steps=10, rounds=6):
     K, B, scale = SHAPES[name]
     dev = torch.device("cuda")
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale, seed=0))
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.bg, sc.esf
+    gg, mg, ag = sc.grid_grad, sc.mlp_grad, sc.gate_grad
     target = torch.rand(B, 3, generator=torch.Generator().manual_seed(7)).to(dev)
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
     rs = {k: FusedMLRenderer(m, g, B) for k in LEGS}
     rs["all_live"]._route_always = True
 
@@ -71,32 +58,19 @@ def run(name, steps=10, rounds=6):
         rs[k].train_step(o, d, d, target, nz, bg, exp_step_factor=esf, grid_grad=gg, mlp_grad=mg,
                          gate_grad=ag, **LAMBDAS, **LEGS[k])
 
-    times = {k: [] for k in rs}
-    for rnd in range(rounds):
-        for k in rs:
-            step(k)                                 # warm-up of this leg
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                step(k)
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms({k: (lambda k=k: step(k)) for k in rs}, steps, rounds)
     dense_samples = rs["dense"].ws.n_samples()
     out = {"shape": name, "K": K, "rays": B, "scale": scale, "steps": steps, "rounds": rounds - 1,
            "dense_samples": dense_samples, "legs": {}}
     for k, r in rs.items():
-        t = times[k]
         routed = r._routed is not None
-        leg = {"ms": round(float(np.median(t)), 4),
-               "range_ms": [round(float(min(t)), 4), round(float(max(t)), 4)],
-               "routed_launches": routed, "scatter_mode": r.scatter_mode,
+        leg = {**times[k], "routed_launches": routed, "scatter_mode": r.scatter_mode,
                "live_pairs": (float(r.ws.route_buffers()["count"].sum()) / (B * K)
                               if routed else 1.0),
                "live_samples": round(r.ws.n_samples() / max(dense_samples, 1), 4)}
         if routed:
             leg["route_count"] = r.ws.route_buffers()["count"].tolist()
-        leg["ms_over_dense"] = round(leg["ms"] / float(np.median(times["dense"])), 4)
+        leg["ms_over_dense"] = round(leg["ms"] / times["dense"]["ms"], 4)
         out["legs"][k] = leg
     return out
 
@@ -104,22 +78,13 @@ def run(name, steps=10, rounds=6):
 if __name__ == "__main__":
     args = sys.argv[1:]
     if "--ab" in args:
-        from deterministic_step import ab_default
-        dest = os.path.join(ROOT, "profiles", "routed", "ab_default.txt")
-        if "--ab-out" in args:
-            dest = args[args.index("--ab-out") + 1]
-        rounds = int(args[args.index("--ab-rounds") + 1]) if "--ab-rounds" in args else 3
-        ab_default(args[args.index("--ab") + 1], dest, rounds)
+        ab_main(args, os.path.join(ROOT, "profiles", "routed", "ab_default.txt"))
         sys.exit(0)
     dest = os.path.join(ROOT, "profiles", "routed", "routed_step.jsonl")
     if "--out" in args:
         i = args.index("--out")
         dest = args[i + 1]
         del args[i:i + 2]
-    os.makedirs(os.path.dirname(os.path.abspath(dest)), exist_ok=True)
     for name in args or ["c3", "c5"]:
-        line = json.dumps(run(name))
-        print(line, flush=True)
-        with open(dest, "a") as f:
-            f.write(line + "\n")
+        append_jsonl(dest, run(name))
         torch.cuda.empty_cache()

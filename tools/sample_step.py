@@ -34,10 +34,10 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "to
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pose_demo import ring_cameras  # noqa: E402
 from pose_step import kernel_us  # noqa: E402
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 from radnerf_amd.sampler import TrainImages, sample_batch  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras  # noqa: E402
 from radnerf_amd.trainer import Trainer  # noqa: E402
 
 K, B, SCALE = 2, 8192, 0.5

@@ -25,23 +25,22 @@ whether every ray is inside the bound mass (1 + 2^-20) + K 2^-23.
 
 usage: python tools/sparse_validate_step.py [--out FILE] [--res N] [--only synthetic|trained]
 """
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pose_demo import ring_cameras  # noqa: E402
 from radnerf_amd import layout as LY  # noqa: E402
 from radnerf_amd import sparse_gate  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.evaluate import ImageEvaluator  # noqa: E402
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras  # noqa: E402
 from radnerf_amd.trainer import Trainer  # noqa: E402
+from steptime import append_jsonl, interleaved_ms  # noqa: E402
 from train_demo import batch  # noqa: E402
 
 FORCE = "forced-all-live"
@@ -49,12 +48,10 @@ FORCE = "forced-all-live"
 
 def synthetic_model(K, scale, dev):
     m, g = MNGP(scale, size=K, seed=3), Ray_Gate(K, seed=4)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
+    S.set_bitfields(m, S.bitfields(K, m.cascades, p=0.5, seed=1))
     with torch.no_grad():
         m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
     return m.to(dev), g.to(dev)
 
 
@@ -109,28 +106,17 @@ def measure(tag, m, g, K, scale, radius, runs_of, res, rounds=4, steps=2, gt_of=
         finally:
             sparse_gate.is_dense = real_is_dense
 
-    times = {k: [] for k in runs}
-    for rnd in range(rounds):
-        for name, kw in runs.items():
-            render(kw)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                render(kw)
-            torch.cuda.synchronize()
-            if rnd:
-                times[name].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms({k: (lambda kw=kw: render(kw)) for k, kw in runs.items()}, steps, rounds)
     N = gate.shape[0]
-    dense_ms = float(np.median(times["dense"]))
     gt = None if gt_of is None else gt_of(dirs, pose)
     psnr = lambda a, b: float(-10 * torch.log10(((a.double() - b.double()) ** 2).mean()))
     lines = []
     for name, kw in runs.items():
         out = {"model": tag, "K": K, "scale": scale, "img_wh": [res, res], "run": name,
                "keywords": {k: v for k, v in kw.items() if k != "force"},
-               "ms_per_image": round(float(np.median(times[name])), 3),
-               "spread_ms": [round(float(min(times[name])), 3), round(float(max(times[name])), 3)],
-               "over_dense": round(float(np.median(times[name])) / dense_ms, 4),
+               "ms_per_image": round(times[name]["ms"], 3),
+               "spread_ms": [round(x, 3) for x in times[name]["range_ms"]],
+               "over_dense": round(times[name]["ms"] / times["dense"]["ms"], 4),
                "rounds": rounds - 1, "images_per_round": steps}
         r = render(kw)
         out["samples"] = int(r["total_samples"])
@@ -208,13 +194,10 @@ def main():
     res = int(argv[argv.index("--res") + 1]) if "--res" in argv else 800
     only = argv[argv.index("--only") + 1] if "--only" in argv else None
     dev = torch.device("cuda")
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
 
     def emit(lines):
-        with open(path, "a") as f:
-            for l in lines:
-                print(json.dumps(l), flush=True)
-                f.write(json.dumps(l) + "\n")
+        for l in lines:
+            append_jsonl(path, l)
 
     if only in (None, "synthetic"):
         for tag, K, scale in (("c3-synthetic", 2, 0.5), ("c5-synthetic", 8, 16.0)):

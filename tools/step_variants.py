@@ -17,7 +17,6 @@ import torch  # noqa: E402
 
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.fused import FusedMLRenderer  # noqa: E402
-from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 
 
 def parse(tok):
@@ -33,21 +32,10 @@ def main():
     dev = torch.device("cuda")
     B, K, steps = int(os.environ.get("STEP_B", 8192)), int(os.environ.get("STEP_K", 2)), 10
     scale = float(os.environ.get("STEP_SCALE", 0.5))
-    esf = 1.0 / 256 if scale > 0.5 else 0.0
-    m = MNGP(scale, size=K, seed=3).to(dev)
-    g = Ray_Gate(K, seed=4).to(dev)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
-    with torch.no_grad():
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
-    o, d = (torch.from_numpy(a).to(dev) for a in S.rays(B, scale, seed=0))
-    nz = torch.from_numpy(S.noise(K, B, seed=2)).to(dev)
-    sd = [torch.from_numpy(a).to(dev) for a in S.loss_seeds(B, K, seed=4)]
-    bg = torch.ones(3, device=dev) if esf == 0 else torch.zeros(3, device=dev)
+    sc = S.bench_scene(K, B, scale, dev)
+    m, g, o, d, nz, sd, bg, esf = sc.m, sc.g, sc.o, sc.d, sc.noise, sc.seeds, sc.bg, sc.esf
+    gg, mg, ag = sc.grid_grad, sc.mlp_grad, sc.gate_grad
     r = FusedMLRenderer(m, g, B)
-    gg = torch.zeros_like(m.xyz_encoder.params)
-    mg = torch.zeros_like(m.mlp_params)
-    ag = torch.zeros_like(g.params)
     defaults = {k: getattr(r, k) for v in variants for k in parse(v)}
 
     def step():

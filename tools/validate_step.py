@@ -17,10 +17,8 @@ how far their numbers are apart.
 
 usage: python tools/validate_step.py [--out FILE] [--res N]
 """
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "tools")]
@@ -28,13 +26,14 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from pose_demo import ring_cameras  # noqa: E402
 from radnerf_amd import layout as LY  # noqa: E402
 from radnerf_amd import synthetic as S  # noqa: E402
 from radnerf_amd.evaluate import DEFAULT_CHUNK, ImageEvaluator  # noqa: E402
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
 from radnerf_amd.rays import get_rays  # noqa: E402
 from radnerf_amd.rendering import ml_render  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras  # noqa: E402
+from steptime import append_jsonl, interleaved_ms  # noqa: E402
 
 
 def torch_ssim(pred, target, H, W):
@@ -61,12 +60,10 @@ def run(res=800, steps=5, rounds=6, chunk=DEFAULT_CHUNK):
     dev = torch.device("cuda")
     m = MNGP(scale, size=K, seed=3)
     g = Ray_Gate(K, seed=4)
-    bits = S.bitfields(K, m.cascades, p=0.5, seed=1)
+    S.set_bitfields(m, S.bitfields(K, m.cascades, p=0.5, seed=1))
     with torch.no_grad():
         m.xyz_encoder.params.copy_(torch.from_numpy(S.grid_params(m.xyz_encoder.n_entries)).view(-1))
         m.mlp_params.copy_(torch.from_numpy(S.mlp_params(K, LY.FIELD_PARAMS)))
-        for i in range(K):
-            getattr(m, f"density_bitfield_{i}").copy_(torch.from_numpy(bits[i]))
     m, g = m.to(dev), g.to(dev)
     dirs, poses = (t.to(dev) for t in ring_cameras(4, res))
     pose = poses[1].contiguous()
@@ -90,23 +87,12 @@ def run(res=800, steps=5, rounds=6, chunk=DEFAULT_CHUNK):
                                 "ssim": torch_ssim(image, gt, res, res)}
 
     forms = {"evaluator": evaluator, "composed": composed}
-    times = {k: [] for k in forms}
-    for rnd in range(rounds):
-        for k, fn in forms.items():
-            fn()                                    # warm-up of this form
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            torch.cuda.synchronize()
-            if rnd:                                 # the first round warms everything up
-                times[k].append((time.perf_counter() - t0) / steps * 1e3)
+    times = interleaved_ms(forms, steps, rounds)
     out = {"shape": "c3", "K": K, "scale": scale, "img_wh": [res, res], "chunk": ev.chunk,
            "chunks": -(-N // ev.chunk), "steps": steps, "rounds": rounds - 1,
            "samples": int(ev.render_image(pose)["total_samples"])}
     for k, t in times.items():
-        out[k + "_ms"] = round(float(np.median(t)), 4)
-        out[k + "_spread_ms"] = [round(float(min(t)), 4), round(float(max(t)), 4)]
+        out[k + "_ms"], out[k + "_spread_ms"] = t["ms"], t["range_ms"]
     out["evaluator_over_composed"] = round(out["evaluator_ms"] / out["composed_ms"], 4)
     for k in ("psnr", "ssim"):
         a, b = float(last["evaluator"][k]), float(last["composed"][k])
@@ -136,8 +122,4 @@ if __name__ == "__main__":
     path = argv[argv.index("--out") + 1] if "--out" in argv else \
         os.path.join(ROOT, "profiles", "validate", "validate_step.jsonl")
     res = int(argv[argv.index("--res") + 1]) if "--res" in argv else 800
-    line = json.dumps(run(res=res))
-    print(line, flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "a") as f:
-        f.write(line + "\n")
+    append_jsonl(path, run(res=res))

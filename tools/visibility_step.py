@@ -28,9 +28,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "rad-nerf_amd"), os.path.join(ROOT, "to
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pose_demo import ring_cameras  # noqa: E402
 from pose_step import kernel_us  # noqa: E402
 from radnerf_amd.networks import MNGP, Ray_Gate  # noqa: E402
+from radnerf_amd.synthetic import ring_cameras, set_bitfields  # noqa: E402
 from radnerf_amd.trainer import MAX_SAMPLES, Trainer  # noqa: E402
 
 N_CAMS, RES, HALF = 100, 800, 0.3
@@ -63,10 +63,10 @@ def _state(m):
 
 
 def _restore(m, state):
+    set_bitfields(m, [b for _, b in state])
     with torch.no_grad():
-        for i, (g, b) in enumerate(state):
+        for i, (g, _) in enumerate(state):
             getattr(m, f"density_grid_{i}").copy_(g)
-            getattr(m, f"density_bitfield_{i}").copy_(b)
 
 
 def update_ab(poses, culled_grid, rounds):
