@@ -1051,6 +1051,59 @@ int rn_mark_invisible_cells(const float* poses, int32_t n_cams, float fx, float 
                             int32_t cascades, int32_t grid_size, float scale, float* count_grid,
                             int32_t* n_culled, void* stream);
 
+/* ---- LPIPS (VGG) (train_ml.py:64-70, --eval_lpips) --------------------------
+ * The pieces of the LPIPS distance of the `lpips` package 0.1, net vgg: the
+ * input step, VGG16's 3 x 3 convolutions, its 2 x 2 max-pool and the per-tap
+ * distance (radnerf_amd/lpips.py composes them).  Activations are f16,
+ * (n_img, H, W, C) row-major with the channels innermost; every accumulation
+ * is fp32; no entry uses an atomic, so a result is a function of the inputs
+ * alone.  Invalid arguments give status 1 and nothing is written; nothing
+ * synchronises with the host.
+ * rn_lpips_prepare: rgb (n_pix, 3) fp32 -> out_f16 (n_pix, 3) f16.  Per
+ * element of channel c, fp32, every operation rounded on its own:
+ *   v = min(max(2 x - 1, -1), 1);  y = (v - shift[c]) / scale[c]  (a division)
+ * with shift = (-.030, -.088, -.188), scale = (.458, .448, .450) as fp32
+ * constants; y is rounded to f16 once.  n_pix == 0 is a valid no-op.
+ * rn_conv3x3_relu_f16: out = relu(conv3x3(in) + bias) for n_img images in one
+ * launch: stride 1, zero padding 1, in (n_img, H, W, Cin) -> out (n_img, H, W,
+ * Cout), both f16.  Per output element the 9 Cin products are summed in fp32
+ * (on v_mfma_f32_32x32x16_f16: f16 products are exact, the order is the
+ * kernel's), then acc + bias[co] in fp32, max(., 0), one rounding to f16.
+ * Cin is 3 (the first layer: its 27-long reduction is padded to 32 inside) or
+ * a multiple of 64; Cout is a multiple of 64: no other padding of C exists,
+ * the buffers hold exactly Cin and Cout channels per pixel.  bias: Cout fp32.
+ * wfrag: the weights as MFMA A-operand fragments of 64 lanes x 8 halfs (1 KiB,
+ * lane-linear).  Lane l (r = l & 31, h = l >> 5), element j of fragment
+ *   Cin >= 64: ((ct (Cin / 64) + chunk) 9 + tap) 4 + ks
+ *              = W[32 ct + r][64 chunk + 16 ks + 8 h + j][tap / 3][tap % 3]
+ *   Cin == 3:  2 ct + ks = W[32 ct + r][k % 3][(k / 3) / 3][(k / 3) % 3] with
+ *              k = 16 ks + 8 h + j, zero for k >= 27
+ * for W (Cout, Cin, 3, 3) (cross-correlation, as torch's conv2d), ct < Cout /
+ * 32: 9 Cin Cout halfs (Cin == 3: 32 Cout).  in and wfrag 16-byte aligned (in:
+ * 2-byte for Cin == 3), out 8-byte.  in and out must not overlap.
+ * rn_maxpool2_f16: in (n_img, H, W, C) -> out (n_img, H / 2, W / 2, C), the
+ * maximum of each 2 x 2 block, floor sizes (an odd last row or column is
+ * dropped); exact.  H, W >= 2; C a multiple of 8; both 16-byte aligned.
+ * rn_lpips_layer: one tap's distance summed over its pixels.  feat0, feat1
+ * (n_pix, C) f16, C a multiple of 8, 16-byte aligned; lin_w: C fp32 (the
+ * non-negative 1 x 1 `lin` weights).  Per pixel, fp32, every operation rounded
+ * on its own: s = sum_c f_c^2, den = sqrt(s) + 1e-10, n_c = f_c / den (a
+ * division) for both images, d = sum_c w_c (n0_c - n1_c)^2; a pixel whose
+ * features are all zero gives n = 0 / 1e-10 = 0.  The channel sums run in a
+ * fixed order (eight interleaved partial sums of every eighth group of 8
+ * channels, then a fixed tree).  out_sum (one device double, written) = the
+ * sum of d over the pixels: per-block partials added in a fixed order in
+ * double (divide by n_pix for the tap's term).  Equal features give exactly
+ * 0.  work: RN_METRICS_WORK_BYTES of device scratch, as rn_image_sse.         */
+int rn_lpips_prepare(const float* rgb, int64_t n_pix, void* out_f16, void* stream);
+int rn_conv3x3_relu_f16(const void* in, const void* wfrag, const float* bias, int32_t n_img,
+                        int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* out,
+                        void* stream);
+int rn_maxpool2_f16(const void* in, int32_t n_img, int32_t H, int32_t W, int32_t C, void* out,
+                    void* stream);
+int rn_lpips_layer(const void* feat0, const void* feat1, const float* lin_w, int64_t n_pix,
+                   int32_t C, void* work, double* out_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,11 @@ SIGNATURES = {
     "rn_scatter_max": [P, P, I64, P, P],
     "rn_mark_invisible_cells": [P, I32, F32, F32, F32, F32, I32, I32, F32, P, P, I32, I32, I32,
                                 F32, P, P, P],
+    # LPIPS (VGG) (lpips.LPIPS)
+    "rn_lpips_prepare": [P, I64, P, P],
+    "rn_conv3x3_relu_f16": [P, P, P, I32, I32, I32, I32, I32, P, P],
+    "rn_maxpool2_f16": [P, I32, I32, I32, I32, P, P],
+    "rn_lpips_layer": [P, P, P, I64, I32, P, P, P],
 }
 
 ABI_VERSION = 9

@@ -222,11 +222,16 @@ class ImageEvaluator:
         return res
 
     def evaluate(self, pose, rgb_gt, T_threshold=1e-4, max_samples=MAX_SAMPLES, gate_min=0.0,
-                 gate_topk=None, renormalize=False):
+                 gate_topk=None, renormalize=False, lpips=None):
         """validation_step's two numbers for one image: rgb_gt (H*W, 3) fp32
         on the device -> {"psnr", "ssim"} (device fp64 scalars).  gate_min /
-        gate_topk / renormalize: the gate-sparse render, as render_image."""
+        gate_topk / renormalize: the gate-sparse render, as render_image.
+        lpips: a radnerf_amd.lpips.LPIPS of this camera's size adds "lpips"
+        (--eval_lpips); None launches and returns nothing more."""
         fn = "ImageEvaluator.evaluate"
+        if lpips is not None:
+            from .lpips import check_metric
+            check_metric(fn, lpips, self.img_wh)
         if not torch.is_tensor(rgb_gt) or tuple(rgb_gt.shape) != (self.n_pix, 3):
             raise ValueError(f"{fn}: rgb_gt must be a ({self.n_pix}, 3) tensor, got "
                              f"{tuple(getattr(rgb_gt, 'shape', ()))}")
@@ -235,7 +240,10 @@ class ImageEvaluator:
         _check_pose("ImageEvaluator.evaluate", pose)
         rgb = self.render_image(pose, T_threshold, max_samples, gate_min, gate_topk,
                                 renormalize)["rgb"]
-        return {"psnr": metrics.psnr(rgb, rgb_gt), "ssim": metrics.ssim(rgb, rgb_gt, self.img_wh)}
+        out = {"psnr": metrics.psnr(rgb, rgb_gt), "ssim": metrics.ssim(rgb, rgb_gt, self.img_wh)}
+        if lpips is not None:
+            out["lpips"] = lpips(rgb, rgb_gt)
+        return out
 
     def images8(self, swap_rb=False, hard_gate=False):
         """The pictures validation_step saves (train_ml.py:238-248), from the

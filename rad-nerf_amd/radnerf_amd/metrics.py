@@ -6,6 +6,7 @@ data_range=1)), on the renderer's own layout -- rgb (H*W, C) row-major, C = 3.
     psnr(pred, target)                         -> device scalar (fp64)
     ssim(pred, target, img_wh, return_map=False)
     ImageMetrics().update(pred, target, img_wh) / .compute() / .reset()
+    ImageMetrics(lpips=lp): also "lpips" (lpips.py), off by default
 
 rn_image_sse and rn_ssim (csrc/metrics.hip) sum fixed-order block partials in
 double without atomics: two calls give the same bits, and nothing synchronises
@@ -112,9 +113,15 @@ class ImageMetrics:
     """Accumulator over validation images (the per-image logging and the mean
     of train_ml.py:214-258): update() per image, compute() -> {"psnr": mean,
     "ssim": mean, "per_image": [{"psnr", "ssim"}, ...]} (device fp64 scalars;
-    the means are of the per-image values), reset()."""
+    the means are of the per-image values), reset().  lpips: a
+    radnerf_amd.lpips.LPIPS of the images' size adds "lpips" to every entry
+    and to the mean; None (the default) launches and returns nothing more."""
 
-    def __init__(self):
+    def __init__(self, lpips=None):
+        if lpips is not None:
+            from .lpips import check_metric
+            check_metric("ImageMetrics", lpips)
+        self.lpips = lpips
         self.reset()
 
     def reset(self):
@@ -122,13 +129,19 @@ class ImageMetrics:
 
     def update(self, pred, target, img_wh):
         _check_image("ImageMetrics.update", pred, target, img_wh)
+        if self.lpips is not None:
+            from .lpips import check_metric
+            check_metric("ImageMetrics.update", self.lpips, img_wh)
         m = {"psnr": psnr(pred, target), "ssim": ssim(pred, target, img_wh)}
+        if self.lpips is not None:
+            m["lpips"] = self.lpips(pred, target)
         self.per_image.append(m)
         return m
 
     def compute(self):
         if not self.per_image:
             raise ValueError("ImageMetrics.compute: no image was given to update()")
-        out = {k: torch.stack([m[k] for m in self.per_image]).mean() for k in ("psnr", "ssim")}
+        keys = ("psnr", "ssim") if self.lpips is None else ("psnr", "ssim", "lpips")
+        out = {k: torch.stack([m[k] for m in self.per_image]).mean() for k in keys}
         out["per_image"] = list(self.per_image)
         return out

@@ -117,6 +117,8 @@ def _world():
 class Trainer:
     # fit(): where its validations write their images (validate's save_dir); None: nowhere
     val_save_dir = None
+    # fit(): a radnerf_amd.lpips.LPIPS its validations also report (validate's lpips); None: off
+    val_lpips = None
     # fit_resumable(ckpt_dir=...): write the checkpoints with save_state(background=True)
     ckpt_background = True
     # routed training (Trainer(gate_topk=, gate_min=, renormalize=,
@@ -700,7 +702,7 @@ class Trainer:
                 getattr(self, k).copy_(v.to(self.device, torch.float32))
 
     def validate(self, poses, images, T_threshold=1e-4, save_dir=None, epoch=0, swap_rb=False,
-                 hard_gate=False, gate_min=0.0, gate_topk=None, renormalize=False):
+                 hard_gate=False, gate_min=0.0, gate_topk=None, renormalize=False, lpips=None):
         """validation_step (train_ml.py:214-250) over (pose, image) pairs:
         poses (N, 3, 4) camera-to-world, used as they are (the test split's own
         poses: no dR / dT, as the reference), images (N, H*W, 3) fp32 (or a
@@ -717,7 +719,11 @@ class Trainer:
         are the same.  Without it nothing more is launched or allocated.
         gate_min / gate_topk / renormalize: the gate-sparse render of
         ImageEvaluator.render_image (sparse_gate.py); the defaults render every
-        sub-NeRF on every ray."""
+        sub-NeRF on every ray.
+        lpips: a radnerf_amd.lpips.LPIPS of the camera's size (--eval_lpips):
+        "lpips" joins the mean and every per_image entry; None (the default)
+        launches and allocates nothing more and returns exactly the keys
+        above."""
         from .evaluate import ImageEvaluator
         from .metrics import ImageMetrics
         if self.directions is None or self.img_wh is None:
@@ -738,6 +744,9 @@ class Trainer:
                                  f"{tuple(getattr(im, 'shape', ()))}")
             if im.dtype != torch.float32 or not im.is_contiguous():
                 raise ValueError(f"Trainer.validate: images[{i}] must be contiguous float32")
+        if lpips is not None:
+            from .lpips import check_metric
+            check_metric("Trainer.validate", lpips, self.img_wh)
         if self._evaluator is None:
             self._evaluator = ImageEvaluator(self.model, self.gate, self.directions, self.img_wh,
                                              exp_step_factor=self.esf)
@@ -745,7 +754,7 @@ class Trainer:
         if save_dir is not None:
             from .imageout import ImageSaver
             saver = ImageSaver(save_dir)
-        acc = ImageMetrics()
+        acc = ImageMetrics(lpips=lpips)
         for i, (pose, im) in enumerate(zip(poses, images)):
             im = im.to(self.device)
             rgb = self._evaluator.render_image(pose, T_threshold, gate_min=gate_min,
@@ -787,7 +796,8 @@ class Trainer:
         {"psnr", "ssim"} as floats.  callback(entry) is called once per epoch.
         With `val_save_dir` set on the trainer (None by default) each
         validation also writes its images there, named by the epoch (validate's
-        save_dir and epoch).
+        save_dir and epoch); with `val_lpips` set (a radnerf_amd.lpips.LPIPS,
+        None by default) each validation entry also holds "lpips".
         The batches depend on (seed, global_step, rank) alone, so a run
         resumed by fit_resumable(..., resume=...) (load_state underneath)
         continues the stream.
@@ -882,9 +892,11 @@ class Trainer:
                      else math.inf}
             if val_poses is not None and ((epoch + 1) % val_every == 0
                                           or epoch == num_epochs - 1):
+                # (lpips only when it is set: off, the call is the one without it)
+                more = {} if self.val_lpips is None else {"lpips": self.val_lpips}
                 val = self.validate(val_poses, val_images, save_dir=self.val_save_dir,
-                                    epoch=epoch)
-                entry["val"] = {k: float(val[k]) for k in ("psnr", "ssim")}
+                                    epoch=epoch, **more)
+                entry["val"] = {k: float(val[k]) for k in ("psnr", "ssim", *more)}
             log.append(entry)
             self._fit_progress = dict(mine, next_epoch=epoch + 1, log=log)
             if ckpt_dir is not None and _rank() == 0 and (
