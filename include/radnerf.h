@@ -247,7 +247,14 @@ int rn_field_bwd(const float* xyzs, const float* dirs, int64_t n_samples, const 
  * count: >= head_chunks + total/max_chunk + total/(8*min_chunk) + max_chunk/min_chunk + 3
  * (+ balance_blocks when balancing): the last big chunk can leave up to
  * max_chunk more samples to the min_chunk tail.  A smaller cap
- * truncates the schedule: the samples past it are not scattered.  With prep (optional, [total] x 4 f32)
+ * truncates the schedule: chunks 0 .. cap_chunks - 1 are those of the full
+ * schedule unchanged (the last kept chunk ends where chunk cap_chunks would
+ * have begun, chunk_first[cap_chunks] is that ray, and no chunk exceeds
+ * max_chunk + n_models * max_samples samples); the rays from there on are in
+ * no chunk, so their samples are neither computed by rn_field_fwd_merged nor
+ * scattered by rn_field_bwd_merged.  queue[1] == cap_chunks is the only sign
+ * of a truncated plan (a cap that is exactly the chunk count reads the same).
+ * mstart, perm and prep do not depend on the cap.  With prep (optional, [total] x 4 f32)
  * it also writes each merged position's (unit x, y, z, sample id as i32 bits)
  * for rn_field_fwd_levels (then called with prep_ready = 1): rays_o, rays_d
  * (device) and xyz_min, extent (host, 3 f32 each) are needed only then.

@@ -389,6 +389,9 @@ __host__ __device__ __forceinline__ ChunkPlan chunk_plan(int total, int head_n, 
 #ifndef RN_TAIL_SHIFT              // (timing studies: -D overrides the tail's share, 2^-shift)
 #define RN_TAIL_SHIFT 4
 #endif
+    // the cap_chunks bound of include/radnerf.h (total / (8 min_chunk) tail chunks) and
+    // Workspace.chunk_list assume a tail of at most 1/8 of the work
+    static_assert(RN_TAIL_SHIFT >= 3, "the documented cap_chunks bound assumes a tail <= 1/8");
     const int main_end = total - (RN_TAIL_SHIFT < 31 ? total >> RN_TAIL_SHIFT : 0);
     // the ramp takes ~head (head_n + 1) / 2 positions: none if that is past the main part
     p.head_n = head > 0 && (int64_t)head * (head_n + 1) / 2 <= main_end ? head_n : 0;
@@ -417,19 +420,23 @@ k_bwd_chunks(int B, int K, const int32_t* __restrict__ mstart,
     const int n = min(p.n, cap_chunks);
     if (c == 0) { queue[0] = 0; queue[1] = n; queue[2] = 0; }
     if (c > n) return;
-    if (c == n) { chunk_first[c] = B; return; }
-    // first ray with mstart >= bound, for this chunk and the next
-    int first[2];
-    for (int e = 0; e < 2; ++e) {
-        if (c + e == n) { first[e] = B; continue; }
-        const int bound = p.bound(c + e);
+    // first ray with mstart >= bound(cc); the complete schedule ends at B (the
+    // rays without samples after the last sample belong to its last chunk).
+    // A schedule cut short by cap_chunks (n < p.n) ends where chunk n would
+    // have begun: its last chunk is the full schedule's, not the rest of the
+    // rays (which would outgrow the scratch rows of rn_field_bwd_merged)
+    auto first_ray = [&](int cc) {
+        if (cc == p.n) return B;
+        const int bound = p.bound(cc);
         int lo = 0, hi = B;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
             if (mstart[mid] < bound) lo = mid + 1; else hi = mid;
         }
-        first[e] = lo;
-    }
+        return lo;
+    };
+    if (c == n) { chunk_first[c] = first_ray(c); return; }
+    const int first[2] = {first_ray(c), first_ray(c + 1)};
     chunk_first[c] = first[0];
     // descriptor: the chunk's sample range per model (the blocks read it with
     // one 80-B load per ticket)

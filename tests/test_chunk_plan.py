@@ -1,11 +1,11 @@
 """CPU: the merged backward's chunk schedule (field_plan.hip chunk_plan, restated
-on the host in test_gpu_ml._chunk_bounds) never needs more chunk slots than
+on the host in plan_ref.chunk_bounds) never needs more chunk slots than
 include/radnerf.h's cap_chunks bound, which Workspace.chunk_list allocates
 (the old bound lacked the tail that the last big chunk can leave
 to min_chunk pieces, and k_bwd_chunks truncates silently past the cap)."""
 import numpy as np
 
-from test_gpu_ml import _chunk_bounds
+from plan_ref import chunk_bounds as _chunk_bounds
 
 
 def header_cap(total, head_n, max_chunk, min_chunk, blocks):

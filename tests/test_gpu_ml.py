@@ -19,6 +19,7 @@ from radnerf_amd import synthetic as S
 from radnerf_amd.fused import ml_render_fused, get_renderer
 from radnerf_amd.rendering import ml_render as _ml_render
 from parity import LAYERS, check_grads, rel as _rel  # noqa: F401
+from plan_ref import chunk_bounds as _chunk_bounds
 
 
 def ml_render(*a, **kw):
@@ -345,35 +346,6 @@ def test_merged_backward_chunking(cuda):
         for i, (a, b) in enumerate(zip(other, res[0])):
             rel = (a - b).norm() / b.norm().clamp_min(1e-30)
             assert rel <= (FX_LEVEL_TOL if i == 0 else 1e-5), rel
-
-
-def _chunk_bounds(total, head_n, head, max_chunk, min_chunk, blocks):
-    """host restatement of field_plan.hip chunk_plan: the merged-position bound of
-    every chunk (head chunks ramping from ~0 to head, big chunks over 15/16 of
-    the work -- with blocks > 0 a multiple of blocks in number, each <=
-    max_chunk -- then min_chunk)"""
-    main_end = total - total // 16
-    head_n = head_n if head > 0 and head * (head_n + 1) // 2 <= main_end else 0
-
-    def hbound(c):
-        return (head * c * (c + 1)) // (2 * head_n) if head_n else 0
-    H = hbound(head_n)
-    big, mm = max_chunk, 0
-    if blocks > 0 and main_end > H:
-        per = blocks * max_chunk
-        mm = -(-(main_end - H) // per)
-        big = min(max(-(-(main_end - H) // (blocks * mm)), min_chunk), max_chunk)
-    c1 = head_n + ((main_end - H) // big if main_end > H else 0)
-
-    def bound(c):
-        if c < head_n:
-            return hbound(c)
-        if c <= c1:
-            return H + (c - head_n) * big
-        return H + (c1 - head_n) * big + (c - c1) * min_chunk
-    rest = total - bound(c1)
-    n = c1 + (-(-rest // min_chunk) if rest > 0 else 0)
-    return [bound(c) for c in range(n)], c1 - head_n, big, mm
 
 
 @pytest.mark.parametrize("B,K,scale,mc,bal,head", [(2048, 2, 0.5, 1536, 256, None),
