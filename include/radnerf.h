@@ -1058,6 +1058,71 @@ int rn_mark_invisible_cells(const float* poses, int32_t n_cams, float fx, float 
                             int32_t cascades, int32_t grid_size, float scale, float* count_grid,
                             int32_t* n_culled, void* stream);
 
+/* ---- mesh export (mesh.hip; radnerf_amd/mesh.py) ----------------------------
+ * A lattice has nx x ny x nz cells, (nx + 1)(ny + 1)(nz + 1) < 2^31 points,
+ * x fastest: point (i, j, k) is element i + (nx + 1)(j + (ny + 1) k).  lo and
+ * step are 3 host floats each.  No entry synchronises with the host; invalid
+ * arguments give status 1 and nothing is written.
+ * rn_density_lattice: sigma (points, fp32, written) of the model on the
+ * lattice, one launch.  Point i of an axis lies at lo + (float)i * step (a
+ * multiply, then an add).  weights: n_models host floats; the value is
+ * acc = w_0 sigma_0, then acc = acc + w_k sigma_k for k ascending over the
+ * sub-NeRFs with w_k != 0 (the others are not evaluated; none: zeros), where
+ * sigma_k is rn_field_density's value at the point for sub-NeRF k (the same
+ * clip, encoding, MFMA order and expf).  frags: all n_models <= 16 sub-NeRFs'
+ * fragments, as rn_field_fwd.  The sub-NeRFs share the hash grid, so a point
+ * is encoded once for all of them.
+ * rn_surface_*: naive surface nets of the lattice sigma at the level iso, all
+ * arithmetic fp32, every operation rounded on its own.
+ *   Inside: sigma[p] >= iso (NaN is outside).  Cell (i, j, k), c = i + nx (j +
+ *   ny k), has corner q at offset (q & 1, q >> 1 & 1, q >> 2 & 1) and is active
+ *   iff its corners are not all alike.  Active cells are vertices 0 .. V - 1
+ *   in ascending c.
+ *   Position: over the 12 cell edges in the order axis a = 0, 1, 2 and, within
+ *   an axis, e = 0 .. 3 (bit 0 of e on the lower remaining axis, bit 1 on the
+ *   higher; the edge runs from corner q0 to q1 = q0 | 1 << a): where the ends
+ *   differ in insideness, t = (iso - s0) / (s1 - s0), t = fminf(fmaxf(t, 0),
+ *   1) (NaN gives 0); the crossing is q0's offset with component a replaced by
+ *   t; crossings are summed in that order and counted.  Lattice position
+ *   (i, j, k) + sum / count, world position lo + position * step.
+ *   Normal: g_a = the sum over the four a-edges, e = 0 .. 3, of (s1 - s0);
+ *   n = -g / sqrtf((gx^2 + gy^2) + gz^2), or (0, 0, 0) when g is not finite or
+ *   the norm is not positive: normals point from dense to empty.
+ *   Faces: the lattice edge from point P along axis a emits a quad iff its
+ *   ends differ in insideness, P_a <= n_a - 1 and, with b = (a + 1) % 3,
+ *   c = (a + 2) % 3, 1 <= P_b <= n_b - 1 and 1 <= P_c <= n_c - 1 (boundary
+ *   edges emit nothing).  Its four cells share a-coordinate P_a and have
+ *   (b, c) offsets v0 (-1, -1), v1 (0, -1), v2 (0, 0), v3 (-1, 0); the quad is
+ *   (v0, v1, v2, v3) if P is inside (the surface faces +a), else (v0, v3, v2,
+ *   v1); quad (q0, q1, q2, q3) is the triangles (q0, q1, q2), (q0, q2, q3) in
+ *   adjacent rows.  Quads are ordered by ascending 3 p + a, p the linear index
+ *   of P.
+ * Both orders come from exclusive scans, no atomic is used: the same lattice
+ * gives the same bits on every call.
+ * rn_surface_work_bytes: *bytes (host) = the size of `work` for the lattice,
+ * 592 B per 1024 points plus 32 (0.58 B per point); no device work.
+ * rn_surface_count: classifies the lattice into work and leaves the counts in
+ * its first two int64: work[0] = V, work[1] = the number of quads (F = twice
+ * that).  The caller reads them (the only synchronisation of an extraction)
+ * and sizes the outputs.
+ * rn_surface_emit: after rn_surface_count on the same lattice, iso and work:
+ * vertices (n_vertices, 3) fp32, normals (n_vertices, 3) fp32 or NULL, faces
+ * (2 n_quads, 3) int32, all written.  n_vertices and n_quads are the rows the
+ * outputs hold (rows past them are not written); n_vertices and 2 n_quads
+ * must be below 2^31.                                                         */
+int rn_density_lattice(int32_t nx, int32_t ny, int32_t nz, const float* lo, const float* step,
+                       const float* weights, int32_t n_models, const void* grid_f16,
+                       const uint32_t* level_offset, const uint32_t* level_hsize,
+                       const uint32_t* level_res, const float* level_scale, const float* xyz_min,
+                       const float* extent, const void* frags, float* sigma, void* stream);
+int rn_surface_work_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t* bytes);
+int rn_surface_count(const float* sigma, int32_t nx, int32_t ny, int32_t nz, float iso,
+                     void* work, void* stream);
+int rn_surface_emit(const float* sigma, int32_t nx, int32_t ny, int32_t nz, float iso,
+                    const float* lo, const float* step, const void* work, int64_t n_vertices,
+                    int64_t n_quads, float* vertices, float* normals, int32_t* faces,
+                    void* stream);
+
 /* ---- LPIPS (VGG) (train_ml.py:64-70, --eval_lpips) --------------------------
  * The pieces of the LPIPS distance of the `lpips` package 0.1, net vgg: the
  * input step, VGG16's 3 x 3 convolutions, its 2 x 2 max-pool and the per-tap

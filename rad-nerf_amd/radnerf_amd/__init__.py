@@ -11,6 +11,7 @@ this package is the Python host side mirroring the reference's interfaces:
   evaluate           whole-image validation render (ImageEvaluator)
   metrics            PSNR / SSIM of validation_step on the device
   imageout           8-bit rgb / depth2img / gate map on the device, PNG files
+  mesh               geometry export: density lattice, surface nets, PLY / OBJ
   sampler            a training step's inputs from device-resident images
                      (TrainImages / sample_batch), the cosine lr schedule
 """

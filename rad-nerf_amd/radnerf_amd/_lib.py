@@ -135,6 +135,11 @@ SIGNATURES = {
     "rn_scatter_max": [P, P, I64, P, P],
     "rn_mark_invisible_cells": [P, I32, F32, F32, F32, F32, I32, I32, F32, P, P, I32, I32, I32,
                                 F32, P, P, P],
+    # mesh export (mesh.density_lattice, mesh.surface_nets)
+    "rn_density_lattice": [I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, P],
+    "rn_surface_work_bytes": [I32, I32, I32, P],
+    "rn_surface_count": [P, I32, I32, I32, F32, P, P],
+    "rn_surface_emit": [P, I32, I32, I32, F32, P, P, P, I64, I64, P, P, P, P],
     # LPIPS (VGG) (lpips.LPIPS)
     "rn_lpips_prepare": [P, I64, P, P],
     "rn_conv3x3_relu_f16": [P, P, P, I32, I32, I32, I32, I32, P, P],

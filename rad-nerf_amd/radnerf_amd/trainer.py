@@ -701,6 +701,16 @@ class Trainer:
             for k, v in poses.items():
                 getattr(self, k).copy_(v.to(self.device, torch.float32))
 
+    def export_mesh(self, path, **kw):
+        """The model's iso-surface as a .ply / .obj file (mesh.extract_mesh's
+        arguments: resolution, iso, aabb, weights, normals, colors); returns the
+        Mesh.  Reads the model only: parameters, grids and the optimiser's state
+        are left as they are."""
+        from .mesh import extract_mesh
+        mesh = extract_mesh(self.model, **kw)
+        mesh.save(path)
+        return mesh
+
     def validate(self, poses, images, T_threshold=1e-4, save_dir=None, epoch=0, swap_rb=False,
                  hard_gate=False, gate_min=0.0, gate_topk=None, renormalize=False, lpips=None):
         """validation_step (train_ml.py:214-250) over (pose, image) pairs:
