@@ -1123,6 +1123,87 @@ int rn_surface_emit(const float* sigma, int32_t nx, int32_t ny, int32_t nz, floa
                     int64_t n_quads, float* vertices, float* normals, int32_t* faces,
                     void* stream);
 
+/* ---- mesh clean-up (mesh.hip, mesh_clean.hip; radnerf_amd/mesh.py) ----------
+ * rn_density_lattice_masked: rn_density_lattice with the occupancy bitfields
+ * as a mask.  bitfields: n_models host pointers to the sub-NeRFs' device
+ * bitfields (cascades * grid_size^3 / 8 bytes each, Morton order; read only for
+ * w_k != 0); grid_size is a power of two.  sigma_k at a lattice point (x, y, z)
+ * counts as exactly 0 when the point's cell in sub-NeRF k's bitfield is clear.
+ * The cell is the one the march queries for the position, the dt term dropped:
+ *   mip = min(cascades - 1, max(0, e + 1)), frexpf(max(|x|, |y|, |z|), &e)
+ *   mbi = 1 / min(2^(mip - 1), scale)
+ *   n_c = (int)fmaxf(0, fminf(0.5f * fmaf(c, mbi, 1.0f) * grid_size,
+ *                             grid_size - 1))            per axis c = x, y, z
+ *   idx = mip * grid_size^3 + morton3d(n_x, n_y, n_z); the bit is idx & 7 of
+ *   byte idx >> 3.
+ * The value is acc = w_0 s_0, then acc = acc + w_k s_k as rn_density_lattice
+ * adds them, with s_k = live ? sigma_k : 0: where every cell is set the result
+ * has rn_density_lattice's bits.  A tile of 32 consecutive points that is dead
+ * for every live sub-NeRF is written as zeros without being encoded.
+ * rn_mesh_*: the connected components of a triangle mesh and the compaction of
+ * some of them.  faces: (F, 3) int32 on the device, V vertices, 1 <= V < 2^31,
+ * 0 <= F < 2^31.  A face with an index outside [0, V) is never dereferenced:
+ * it joins nothing, belongs to no component, is never kept, and raises
+ * work[0].  No entry synchronises with the host.
+ *   Connectivity: two vertices are connected when some face holds both;
+ *   components are the transitive closure; a vertex in no face is a component
+ *   of its own.  root[v] is the lowest vertex index of v's component.
+ *   Components are numbered 0 .. C - 1 in ascending order of root (an
+ *   exclusive scan over the flags root[v] == v); label[v] is the number of
+ *   v's component, comp_vertices[c] and comp_faces[c] its sizes, a face
+ *   counting for the component of its vertices.
+ *   Compaction: keep[c] != 0 keeps component c.  Kept vertices keep their
+ *   relative order (new index = the exclusive scan of the kept flags), kept
+ *   faces theirs, with indices remapped; normals and colors rows travel with
+ *   their vertices.
+ * Every order comes from a scan; the atomics used (integer min, add, or) give
+ * results that do not depend on order: the same mesh gives the same bits on
+ * every call, and label does not depend on the order of the face rows.
+ * work: int64 words, work[0] = some face index is out of range, work[1] = the
+ * labelling has not converged, work[2] = C, work[3], work[4] = kept vertices,
+ * kept faces; the scan tables follow.
+ * rn_mesh_work_bytes: *bytes (host) = the size of work, 64 + 168 B per 1024
+ * vertices and per 1024 faces; no device work.
+ * rn_mesh_label: with restart != 0 sets root[v] = v and work[0]; then `rounds`
+ * rounds of (hook: the lowest of a face's three labels onto its vertices and
+ * onto the vertices those labels name, by atomicMin; jump: root[v] = the
+ * label of the label of root[v], by atomicMin), then one check that writes
+ * work[1] (0 iff every face has three equal labels and root[root[v]] ==
+ * root[v] everywhere: then root is as defined above) and work[2].  A label only
+ * ever decreases to a vertex of the same component, so a stale read costs a
+ * round and nothing else; no kernel waits on another workgroup or loops
+ * without a bound known at launch.  The caller launches batches (restart = 0
+ * after the first) until work[1] == 0.
+ * rn_mesh_components: after convergence, n_components = work[2]: label (V)
+ * int32, comp_vertices and comp_faces (n_components) int64, all written.
+ * rn_mesh_compact_count: marks the kept vertices and faces in work and leaves
+ * their numbers in work[3], work[4] for the caller to size the outputs.
+ * rn_mesh_compact_emit: after rn_mesh_compact_count on the same mesh and work:
+ * out_vertices (kept_vertices, 3) fp32, out_faces (kept_faces, 3) int32, and
+ * out_normals fp32 / out_colors uint8 where normals / colors are not NULL;
+ * rows past the kept counts given are not written.                            */
+int rn_density_lattice_masked(int32_t nx, int32_t ny, int32_t nz, const float* lo,
+                              const float* step, const float* weights, int32_t n_models,
+                              const void* grid_f16, const uint32_t* level_offset,
+                              const uint32_t* level_hsize, const uint32_t* level_res,
+                              const float* level_scale, const float* xyz_min, const float* extent,
+                              const void* frags, const void* const* bitfields, int32_t cascades,
+                              int32_t grid_size, float scale, float* sigma, void* stream);
+int rn_mesh_work_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes);
+int rn_mesh_label(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* root,
+                  void* work, int32_t rounds, int32_t restart, void* stream);
+int rn_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_vertices,
+                       const int32_t* root, void* work, int64_t n_components, int32_t* label,
+                       int64_t* comp_vertices, int64_t* comp_faces, void* stream);
+int rn_mesh_compact_count(const int32_t* faces, int64_t n_faces, int64_t n_vertices,
+                          const int32_t* label, const uint8_t* keep, int64_t n_components,
+                          void* work, void* stream);
+int rn_mesh_compact_emit(const int32_t* faces, int64_t n_faces, int64_t n_vertices,
+                         const void* work, const float* vertices, const float* normals,
+                         const uint8_t* colors, int64_t kept_vertices, int64_t kept_faces,
+                         float* out_vertices, float* out_normals, uint8_t* out_colors,
+                         int32_t* out_faces, void* stream);
+
 /* ---- LPIPS (VGG) (train_ml.py:64-70, --eval_lpips) --------------------------
  * The pieces of the LPIPS distance of the `lpips` package 0.1, net vgg: the
  * input step, VGG16's 3 x 3 convolutions, its 2 x 2 max-pool and the per-tap

@@ -16,6 +16,7 @@
 // c = i + nx (j + ny k), so one scan over the points numbers both the
 // vertices (cells) and the quads (3 p + a).
 #include "rn_field.h"
+#include "rn_march.h"
 #pragma clang fp contract(off)
 
 #define ML_KMAX 16         // sub-NeRFs of one MNGP (the gate's rows)
@@ -36,6 +37,33 @@ struct LatticeArgs {
     float w[ML_KMAX];              // and their weights
     float* out;
 };
+
+// the occupancy mask of rn_density_lattice_masked: the live sub-NeRFs' own
+// bitfields, in the order of LatticeArgs.idx, and the march's grid
+struct MaskArgs {
+    const uint8_t* bits[ML_KMAX];
+    int cascades, grid_size;
+    float scale;
+};
+
+// bit q set: the point's cell is set in live sub-NeRF q's bitfield.  The cell
+// is the one march_step (rn_march.h) queries for the position, the dt term
+// dropped.
+__device__ __forceinline__ uint32_t lattice_live(const MaskArgs& m, int n_live, float x, float y,
+                                                 float z) {
+    const int mip = rn_mip_from_pos(x, y, z, m.cascades);
+    const float mbi = mip_bound_inv(mip, m.scale);
+    const float gm1 = m.grid_size - 1.0f;
+    const int nx = (int)rn_clampf(0.5f * fmaf(x, mbi, 1.0f) * m.grid_size, 0.0f, gm1);
+    const int ny = (int)rn_clampf(0.5f * fmaf(y, mbi, 1.0f) * m.grid_size, 0.0f, gm1);
+    const int nz = (int)rn_clampf(0.5f * fmaf(z, mbi, 1.0f) * m.grid_size, 0.0f, gm1);
+    const uint32_t g3 = (uint32_t)m.grid_size * m.grid_size * m.grid_size;
+    const uint32_t idx = mip * g3 + rn_morton3d(nx, ny, nz);
+    uint32_t live = 0;
+    for (int q = 0; q < n_live; ++q)
+        live |= (uint32_t)((m.bits[q][idx >> 3] >> (idx & 7)) & 1) << q;
+    return live;
+}
 
 // acc = w_0 sigma_0, then acc + w_k sigma_k for the live k ascending.  More
 // than ML_LDS_K live sub-NeRFs run in groups: a later group encodes the
@@ -89,6 +117,79 @@ k_density_lattice(FieldArgs a, LatticeArgs g) {
 #pragma unroll
                 for (int qq = 0; qq < 4; ++qq) gg = rn_mfma(rn_frag(sW, 4 + qq), h1[qq], gg);
                 const float t = g.w[q] * expf(gg[8]);
+                acc = q == 0 ? t : acc + t;
+            }
+            if (valid && h == 0) g.out[p] = acc;
+        }
+    }
+}
+
+// k_density_lattice with the occupancy mask, a kernel of its own (the unmasked
+// one carries no mask argument and no test of one): sigma_k counts as 0 where
+// sub-NeRF k's bitfield is clear.  A tile that is dead for the whole group
+// skips the encode and the MLPs, a sub-NeRF dead on the whole tile its MLP;
+// both tests are ballots, wave-uniform, so no divergence surrounds the MFMAs.
+// A live point's terms are the unmasked kernel's, added in its order.
+__global__ void __launch_bounds__(512)
+k_density_lattice_masked(FieldArgs a, LatticeArgs g, MaskArgs m) {
+    extern __shared__ __attribute__((aligned(16))) rn_half sWl[];   // [<= ML_LDS_K][8 geo frags]
+    __shared__ LvTab sT;
+    lv_stage(sT, a.gm);
+    const int64_t n_tiles = (g.n + 31) / 32;
+    const int waves = blockDim.x / RN_WAVE;
+    const int lane = rn_lane(), c = lane & 31, h = lane >> 5;
+    const __amdgpu_buffer_rsrc_t rs = rn_rsrc(a.grid, a.grid_bytes);
+    for (int kb = 0; kb < g.n_live; kb += ML_LDS_K) {
+        const int ke = min(g.n_live, kb + ML_LDS_K);
+        __syncthreads();                                   // the previous group's tiles are done
+        for (int q = kb; q < ke; ++q)
+            rn_block_copy16(sWl + (size_t)(q - kb) * ML_GEO_HALFS,
+                            a.frags + (size_t)g.idx[q] * FIELD_FRAGS * RN_FRAG_HALFS,
+                            8 * RN_FRAG_BYTES);
+        __syncthreads();
+        for (int64_t tile = (int64_t)blockIdx.x * waves + threadIdx.x / RN_WAVE; tile < n_tiles;
+             tile += (int64_t)gridDim.x * waves) {
+            rn_lds_order();
+            const int64_t i = tile * 32 + c;
+            const bool valid = i < g.n;
+            const uint32_t p = valid ? (uint32_t)i : 0u;
+            const uint32_t row = p / g.px, pi = p - row * g.px;
+            const uint32_t pk = row / g.py, pj = row - pk * g.py;
+            // point i of an axis: lo + (float)i * step, a multiply then an add
+            const float x = g.lo[0] + (float)pi * g.step[0];
+            const float y = g.lo[1] + (float)pj * g.step[1];
+            const float z = g.lo[2] + (float)pk * g.step[2];
+            const uint32_t live = valid ? lattice_live(m, g.n_live, x, y, z) : 0u;
+            const uint32_t grp = (live >> kb) & ((1u << (ke - kb)) - 1u);
+            if (__builtin_amdgcn_ballot_w64(grp != 0) == 0) {          // a dead tile
+                if (kb == 0 && valid && h == 0) g.out[p] = 0.f;
+                continue;
+            }
+            const float ux = unit_coord(x, a.xyz_min[0], a.extent[0]);
+            const float uy = unit_coord(y, a.xyz_min[1], a.extent[1]);
+            const float uz = unit_coord(z, a.xyz_min[2], a.extent[2]);
+            half8 e0, e1;
+            encode_lane(a, sT, rs, h, ux, uy, uz, valid, e0, e1);
+            // geo layer 1 is the same for every sub-NeRF only in its input:
+            // the weights differ, so the whole geo MLP runs per sub-NeRF
+            float acc = (kb && valid && h == 0) ? g.out[p] : 0.f;
+            for (int q = kb; q < ke; ++q) {
+                const bool on = (live >> q) & 1;
+                float sg = 0.f;
+                if (__builtin_amdgcn_ballot_w64(on) != 0) {
+                    const rn_half* sW = sWl + (size_t)(q - kb) * ML_GEO_HALFS;
+                    f32x16 a0 = rn_zero16(), a1 = rn_zero16();
+                    a0 = rn_mfma(rn_frag(sW, 0), e0, a0); a0 = rn_mfma(rn_frag(sW, 1), e1, a0);
+                    a1 = rn_mfma(rn_frag(sW, 2), e0, a1); a1 = rn_mfma(rn_frag(sW, 3), e1, a1);
+                    half8 h1[4];
+                    rn_acc_to_frags<true>(a0, h1[0], h1[1]);
+                    rn_acc_to_frags<true>(a1, h1[2], h1[3]);
+                    f32x16 gg = rn_zero16();
+#pragma unroll
+                    for (int qq = 0; qq < 4; ++qq) gg = rn_mfma(rn_frag(sW, 4 + qq), h1[qq], gg);
+                    sg = on ? expf(gg[8]) : 0.f;
+                }
+                const float t = g.w[q] * sg;
                 acc = q == 0 ? t : acc + t;
             }
             if (valid && h == 0) g.out[p] = acc;
@@ -330,6 +431,57 @@ int sn_fill(SurfArgs& u, const char* who, const float* sigma, int32_t nx, int32_
     return 0;
 }
 
+// both lattice entries: `bitfields` null is the unmasked launch
+int lattice_launch(const char* who, int32_t nx, int32_t ny, int32_t nz, const float* lo,
+                   const float* step, const float* weights, int32_t n_models, const void* grid_f16,
+                   const uint32_t* level_offset, const uint32_t* level_hsize,
+                   const uint32_t* level_res, const float* level_scale, const float* xyz_min,
+                   const float* extent, const void* frags, const void* const* bitfields,
+                   int32_t cascades, int32_t grid_size, float scale, float* sigma, void* stream) {
+    RN_CHECK_ARG_AS(who, nx >= 1 && ny >= 1 && nz >= 1 && n_models >= 1 && n_models <= ML_KMAX,
+                    "bad sizes (cells per axis >= 1, n_models <= 16)");
+    const int64_t n = ((int64_t)nx + 1) * ((int64_t)ny + 1) * ((int64_t)nz + 1);
+    RN_CHECK_ARG_AS(who, n < ((int64_t)1 << 31), "lattice of 2^31 points or more");
+    RN_CHECK_ARG_AS(who, lo && step && weights && grid_f16 && level_offset && level_hsize &&
+                    level_res && level_scale && xyz_min && extent && frags && sigma, "null pointer");
+    FieldArgs a{};
+    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
+    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
+    LatticeArgs g{};
+    g.px = nx + 1; g.py = ny + 1; g.n = n; g.out = sigma;
+    for (int d = 0; d < 3; ++d) { g.lo[d] = lo[d]; g.step[d] = step[d]; }
+    for (int k = 0; k < n_models; ++k)
+        if (weights[k] != 0.f) { g.idx[g.n_live] = k; g.w[g.n_live] = weights[k]; ++g.n_live; }
+    MaskArgs m{};
+    if (bitfields) {
+        // Morton codes hold 10 bits per axis; a cascade's bits fill whole bytes
+        RN_CHECK_ARG_AS(who, cascades >= 1 && cascades <= 32 && grid_size >= 2 && grid_size <= 1024 &&
+                        (grid_size & (grid_size - 1)) == 0 && scale > 0.f,
+                        "bad grid (cascades 1 .. 32, grid_size a power of two 2 .. 1024, scale > 0)");
+        for (int q = 0; q < g.n_live; ++q) {
+            m.bits[q] = (const uint8_t*)bitfields[g.idx[q]];
+            RN_CHECK_ARG_AS(who, m.bits[q], "null bitfield");
+        }
+        m.cascades = cascades; m.grid_size = grid_size; m.scale = scale;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (g.n_live == 0) {                                   // the empty sum
+        RN_CHECK_HIP_AS(who, hipMemsetAsync(sigma, 0, sizeof(float) * n, st), "memset");
+        return 0;
+    }
+    const int resident = g.n_live < ML_LDS_K ? g.n_live : ML_LDS_K;
+    // 8 KB of LDS per resident sub-NeRF: wider blocks keep the waves per CU up
+    const int threads = resident <= 4 ? 256 : 512;
+    const int waves = threads / RN_WAVE;
+    const int64_t tiles = (n + 31) / 32;
+    const int blocks = (int)(tiles / waves + 1 < 8192 ? tiles / waves + 1 : 8192);
+    const size_t lds = (size_t)resident * 8 * RN_FRAG_BYTES;
+    if (bitfields) k_density_lattice_masked<<<blocks, threads, lds, st>>>(a, g, m);
+    else k_density_lattice<<<blocks, threads, lds, st>>>(a, g);
+    RN_CHECK_LAUNCH_AS(who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,34 +491,22 @@ int rn_density_lattice(int32_t nx, int32_t ny, int32_t nz, const float* lo, cons
                        const uint32_t* level_offset, const uint32_t* level_hsize,
                        const uint32_t* level_res, const float* level_scale, const float* xyz_min,
                        const float* extent, const void* frags, float* sigma, void* stream) {
-    RN_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && n_models >= 1 && n_models <= ML_KMAX,
-                 "bad sizes (cells per axis >= 1, n_models <= 16)");
-    const int64_t n = ((int64_t)nx + 1) * ((int64_t)ny + 1) * ((int64_t)nz + 1);
-    RN_CHECK_ARG(n < ((int64_t)1 << 31), "lattice of 2^31 points or more");
-    RN_CHECK_ARG(lo && step && weights && grid_f16 && level_offset && level_hsize && level_res &&
-                 level_scale && xyz_min && extent && frags && sigma, "null pointer");
-    FieldArgs a{};
-    fill_args(a, xyz_min, extent, level_offset, level_hsize, level_res, level_scale);
-    a.grid = (const rn_half*)grid_f16; a.frags = (const rn_half*)frags;
-    LatticeArgs g{};
-    g.px = nx + 1; g.py = ny + 1; g.n = n; g.out = sigma;
-    for (int d = 0; d < 3; ++d) { g.lo[d] = lo[d]; g.step[d] = step[d]; }
-    for (int k = 0; k < n_models; ++k)
-        if (weights[k] != 0.f) { g.idx[g.n_live] = k; g.w[g.n_live] = weights[k]; ++g.n_live; }
-    hipStream_t st = (hipStream_t)stream;
-    if (g.n_live == 0) {                                   // the empty sum
-        RN_CHECK_HIP(hipMemsetAsync(sigma, 0, sizeof(float) * n, st), "memset");
-        return 0;
-    }
-    const int resident = g.n_live < ML_LDS_K ? g.n_live : ML_LDS_K;
-    // 8 KB of LDS per resident sub-NeRF: wider blocks keep the waves per CU up
-    const int threads = resident <= 4 ? 256 : 512;
-    const int waves = threads / RN_WAVE;
-    const int64_t tiles = (n + 31) / 32;
-    const int blocks = (int)(tiles / waves + 1 < 8192 ? tiles / waves + 1 : 8192);
-    k_density_lattice<<<blocks, threads, (size_t)resident * 8 * RN_FRAG_BYTES, st>>>(a, g);
-    RN_CHECK_LAUNCH();
-    return 0;
+    return lattice_launch(__func__, nx, ny, nz, lo, step, weights, n_models, grid_f16, level_offset,
+                          level_hsize, level_res, level_scale, xyz_min, extent, frags, nullptr, 0,
+                          0, 0.f, sigma, stream);
+}
+
+int rn_density_lattice_masked(int32_t nx, int32_t ny, int32_t nz, const float* lo,
+                              const float* step, const float* weights, int32_t n_models,
+                              const void* grid_f16, const uint32_t* level_offset,
+                              const uint32_t* level_hsize, const uint32_t* level_res,
+                              const float* level_scale, const float* xyz_min, const float* extent,
+                              const void* frags, const void* const* bitfields, int32_t cascades,
+                              int32_t grid_size, float scale, float* sigma, void* stream) {
+    RN_CHECK_ARG(bitfields, "null pointer");
+    return lattice_launch(__func__, nx, ny, nz, lo, step, weights, n_models, grid_f16, level_offset,
+                          level_hsize, level_res, level_scale, xyz_min, extent, frags, bitfields,
+                          cascades, grid_size, scale, sigma, stream);
 }
 
 int rn_surface_work_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t* bytes) {

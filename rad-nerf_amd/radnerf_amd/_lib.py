@@ -140,6 +140,15 @@ SIGNATURES = {
     "rn_surface_work_bytes": [I32, I32, I32, P],
     "rn_surface_count": [P, I32, I32, I32, F32, P, P],
     "rn_surface_emit": [P, I32, I32, I32, F32, P, P, P, I64, I64, P, P, P, P],
+    # mesh clean-up (mesh.density_lattice(occupancy=True), mesh.components,
+    # mesh.filter_components)
+    "rn_density_lattice_masked": [I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, I32,
+                                  I32, F32, P, P],
+    "rn_mesh_work_bytes": [I64, I64, P],
+    "rn_mesh_label": [P, I64, I64, P, P, I32, I32, P],
+    "rn_mesh_components": [P, I64, I64, P, P, I64, P, P, P, P],
+    "rn_mesh_compact_count": [P, I64, I64, P, P, I64, P, P],
+    "rn_mesh_compact_emit": [P, I64, I64, P, P, P, P, I64, I64, P, P, P, P, P],
     # LPIPS (VGG) (lpips.LPIPS)
     "rn_lpips_prepare": [P, I64, P, P],
     "rn_conv3x3_relu_f16": [P, P, P, I32, I32, I32, I32, I32, P, P],

@@ -5,7 +5,12 @@
                       rn_surface_emit): naive surface nets, one vertex per
                       sign-changing cell, one quad per sign-changing interior
                       lattice edge; the rules are in include/radnerf.h
-    extract_mesh      both, plus per-vertex colours from the model's forward
+    components        the connected components of a mesh (rn_mesh_label /
+                      rn_mesh_components)
+    filter_components keep the largest components, or those above a size
+                      (rn_mesh_compact_count / rn_mesh_compact_emit)
+    extract_mesh      lattice, surface, optionally the filter, plus per-vertex
+                      colours from the model's forward
     Mesh.save         binary little-endian PLY or OBJ (standard library + numpy)
     load_ply/load_obj read back what save wrote
 
@@ -14,9 +19,14 @@ space -- every sub-NeRF is a whole model of the scene and the image is the
 gate-weighted sum of their renders -- so the lattice is a weighted sum of the
 sub-NeRFs' densities, by default their mean (a consensus).  A one-hot `weights`
 gives one sub-NeRF's own surface.  A model trained with routing may hold
-floaters in sub-NeRFs that never saw a region; they are exported as they are.
+floaters in sub-NeRFs that never saw a region: density above the level where
+no ray ever constrained the field.  density_lattice(occupancy=True) drops what
+lies in cells the occupancy grid calls empty, filter_components drops whole
+components by size (surfaces inside the object included, which no occupancy
+test can see).
 """
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -24,7 +34,7 @@ import numpy as np
 import torch
 
 from ._lib import lib
-from .networks import _stream, field_ptrs
+from .networks import _stream, field_ptrs, model_bitfields
 
 # the training density threshold (trainer.py: 0.01 * MAX_SAMPLES / 3 ** 0.5),
 # extract_mesh's default level: a choice, not a property of the model
@@ -226,9 +236,26 @@ def _ptr(a):
     return a.ctypes.data
 
 
+def _bitfields(fn, model):
+    """the sub-NeRFs' occupancy bitfields, checked: occupancy=True needs them"""
+    try:
+        bits = model_bitfields(model)
+        C, G = int(model.cascades), int(model.grid_size)
+        float(model.scale)
+    except (AttributeError, TypeError):
+        raise ValueError(f"{fn}: occupancy=True needs a model with density_bitfield_k buffers, "
+                         f"cascades, grid_size and scale; {type(model).__name__} has none")
+    for k, b in enumerate(bits):
+        if (not torch.is_tensor(b) or b.dtype != torch.uint8 or b.numel() != C * G ** 3 // 8
+                or not b.is_contiguous()):
+            raise ValueError(f"{fn}: density_bitfield_{k} must be {C * G ** 3 // 8} contiguous "
+                             f"uint8 (cascades {C}, grid_size {G})")
+    return bits
+
+
 # ---- the lattice ------------------------------------------------------------------------
 @torch.no_grad()
-def density_lattice(model, resolution, aabb=None, weights=None):
+def density_lattice(model, resolution, aabb=None, weights=None, occupancy=False):
     """sigma of `model` (an MNGP or NGP on the GPU) on a regular lattice ->
     (nz + 1, ny + 1, nx + 1) fp32 on the model's device, x fastest.
 
@@ -237,9 +264,19 @@ def density_lattice(model, resolution, aabb=None, weights=None):
     lo + float32(i) * step with step = (hi - lo) / n in fp32.  weights: (K,)
     fp32, by default 1 / K each; the value is w_0 sigma_0 + w_1 sigma_1 + ...
     added in that order over the sub-NeRFs with a non-zero weight, sigma_k
-    being exactly MNGP.density(x, k).  One launch, no xyz buffer."""
+    being exactly MNGP.density(x, k).  One launch, no xyz buffer.
+
+    occupancy=True: sigma_k counts as exactly 0 where the point's cell in
+    sub-NeRF k's own density_bitfield is clear -- the cell the march would
+    query for that position (rn_density_lattice_masked) -- and a tile of 32
+    points that is dead for every live sub-NeRF is neither encoded nor run
+    through the MLP.  A live point keeps the bits the unmasked lattice gives
+    it.  Caveat: the bitfield is a thresholded, max-pooled, decayed copy of the
+    density, not the density; where the field and the grid disagree the mask
+    cuts a surface at a cell face."""
     fn = "density_lattice"
     res = _resolution(fn, resolution)
+    bits = _bitfields(fn, model) if occupancy else None
     mlo, mhi = _model_box(model)
     lo, step = _box(fn, (mlo, mhi) if aabb is None else aabb, res)
     if aabb is not None:
@@ -252,8 +289,17 @@ def density_lattice(model, resolution, aabb=None, weights=None):
     if dev.type != "cuda":
         raise ValueError(f"{fn}: the model must be on the GPU, got {dev}")
     out = torch.empty(res[2] + 1, res[1] + 1, res[0] + 1, device=dev)
-    lib().density_lattice(res[0], res[1], res[2], _ptr(lo), _ptr(step), _ptr(w), model.size,
-                          *field_ptrs(model), out.data_ptr(), _stream(dev))
+    if bits is None:
+        lib().density_lattice(res[0], res[1], res[2], _ptr(lo), _ptr(step), _ptr(w), model.size,
+                              *field_ptrs(model), out.data_ptr(), _stream(dev))
+        return out
+    if any(b.device != dev for b in bits):
+        raise ValueError(f"{fn}: the bitfields must be on the model's device {dev}")
+    ptrs = (ctypes.c_void_p * model.size)(*[b.data_ptr() for b in bits])
+    lib().density_lattice_masked(res[0], res[1], res[2], _ptr(lo), _ptr(step), _ptr(w),
+                                 model.size, *field_ptrs(model), ptrs, int(model.cascades),
+                                 int(model.grid_size), float(model.scale), out.data_ptr(),
+                                 _stream(dev))
     return out
 
 
@@ -301,6 +347,181 @@ def surface_nets(sigma, iso, aabb, normals=True):
     return Mesh(v, f, nr)
 
 
+# ---- clean-up ---------------------------------------------------------------------------
+@dataclass
+class Components:
+    """label (V,) int32: the component of every vertex; n_vertices, n_faces
+    (C,) int64: the components' sizes.  Components are numbered in ascending
+    order of their lowest vertex index."""
+    label: torch.Tensor
+    n_vertices: torch.Tensor
+    n_faces: torch.Tensor
+
+
+# Rounds of the labelling per batch, and the batches a call may take.  The
+# numpy model of the scheme (tests/mesh_clean_ref.py: label_rounds) needs 5 to
+# 12 rounds on the test meshes, a 4,000-quad strip with permuted indices
+# included, so one batch is the usual case; 16 batches are 192 rounds.
+LABEL_ROUNDS = 12
+LABEL_BATCHES = 16
+
+
+def _faces_arg(fn, faces):
+    if (not torch.is_tensor(faces) or faces.dtype != torch.int32 or faces.dim() != 2
+            or faces.shape[1] != 3):
+        raise ValueError(f"{fn}: faces must be an (F, 3) int32 tensor")
+    if not faces.is_contiguous():
+        raise ValueError(f"{fn}: faces must be contiguous")
+    if faces.shape[0] >= _LIMIT:
+        raise ValueError(f"{fn}: {faces.shape[0]} faces; the limit is below 2^31")
+
+
+def _mesh_arg(fn, mesh):
+    v = getattr(mesh, "vertices", None)
+    if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"{fn}: mesh.vertices must be a (V, 3) float32 tensor")
+    _faces_arg(fn, mesh.faces)
+    V = v.shape[0]
+    if V >= _LIMIT:
+        raise ValueError(f"{fn}: {V} vertices; the limit is below 2^31")
+    for name, dt in (("normals", torch.float32), ("colors", torch.uint8)):
+        t = getattr(mesh, name)
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (V, 3)):
+            raise ValueError(f"{fn}: mesh.{name} must be ({V}, 3) {dt} or None")
+    for t in (v, mesh.faces, mesh.normals, mesh.colors):
+        if t is not None and (t.device != v.device or not t.is_contiguous()):
+            raise ValueError(f"{fn}: the mesh's tensors must be contiguous and on one device")
+    if not v.is_cuda:
+        raise ValueError(f"{fn}: the mesh must be on the GPU, got {v.device}")
+    return V, mesh.faces.shape[0]
+
+
+def _mesh_work(V, F, dev):
+    n = ctypes.c_int64(0)
+    lib().mesh_work_bytes(V, F, ctypes.byref(n))
+    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+
+def _label(fn, faces, V, work, rounds=LABEL_ROUNDS, batches=LABEL_BATCHES):
+    """root (V,) int32 = the lowest vertex index of every vertex's component
+    -> root, C, batches taken.  One host read per batch."""
+    dev, F = faces.device, faces.shape[0]
+    root = torch.empty(V, dtype=torch.int32, device=dev)
+    for b in range(batches):
+        lib().mesh_label(faces.data_ptr() if F else None, F, V, root.data_ptr(), work.data_ptr(),
+                         rounds, int(b == 0), _stream(dev))
+        bad, still, C = work[:24].view(torch.int64).tolist()      # the batch's synchronisation
+        if bad:
+            raise ValueError(f"{fn}: a face holds a vertex index outside [0, {V})")
+        if not still:
+            return root, C, b + 1
+    raise RuntimeError(f"{fn}: the labelling has not converged after {batches} batches of "
+                       f"{rounds} rounds")
+
+
+def _components(fn, mesh):
+    V, F = _mesh_arg(fn, mesh)
+    dev = mesh.vertices.device
+    if V == 0:
+        if F:
+            raise ValueError(f"{fn}: a face holds a vertex index outside [0, 0)")
+        z = lambda dt: torch.empty(0, dtype=dt, device=dev)
+        return Components(z(torch.int32), z(torch.int64), z(torch.int64)), None
+    work = _mesh_work(V, F, dev)
+    root, C, _ = _label(fn, mesh.faces, V, work)
+    label = torch.empty(V, dtype=torch.int32, device=dev)
+    nv = torch.empty(C, dtype=torch.int64, device=dev)
+    nf = torch.empty(C, dtype=torch.int64, device=dev)
+    lib().mesh_components(mesh.faces.data_ptr() if F else None, F, V, root.data_ptr(),
+                          work.data_ptr(), C, label.data_ptr(), nv.data_ptr(), nf.data_ptr(),
+                          _stream(dev))
+    return Components(label, nv, nf), work
+
+
+@torch.no_grad()
+def components(mesh):
+    """The connected components of a device Mesh -> Components.  Two vertices
+    are connected when some face holds both; a vertex in no face is a
+    component of its own; components are numbered in ascending order of their
+    lowest vertex index (include/radnerf.h, rn_mesh_*).  The labelling runs in
+    batches of LABEL_ROUNDS rounds of min-label hooking and pointer jumping and
+    the host reads one flag per batch: usually one synchronisation per call,
+    at most LABEL_BATCHES, then RuntimeError.  A face index outside [0, V) is
+    a ValueError (it is never dereferenced).  The same mesh gives the same
+    bits on every call, whatever the order of its face rows."""
+    return _components("components", mesh)[0]
+
+
+def _criteria(fn, keep_largest, min_vertices, min_fraction):
+    if keep_largest is None and min_vertices is None and min_fraction is None:
+        raise ValueError(f"{fn}: give keep_largest, min_vertices or min_fraction")
+    if keep_largest is not None and (not isinstance(keep_largest, (int, np.integer))
+                                     or isinstance(keep_largest, bool) or keep_largest < 1):
+        raise ValueError(f"{fn}: keep_largest must be an int >= 1, got {keep_largest!r}")
+    if min_vertices is not None and (not isinstance(min_vertices, (int, np.integer))
+                                     or isinstance(min_vertices, bool) or min_vertices < 0):
+        raise ValueError(f"{fn}: min_vertices must be an int >= 0, got {min_vertices!r}")
+    if min_fraction is not None:
+        try:
+            ok = 0.0 <= float(min_fraction) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{fn}: min_fraction must lie in [0, 1], got {min_fraction!r}")
+
+
+def _keep(comp, V, keep_largest, min_vertices, min_fraction):
+    """(C,) uint8 on the device: 1 where every given criterion holds"""
+    nv = comp.n_vertices
+    keep = torch.ones_like(nv, dtype=torch.bool)
+    if min_vertices is not None:
+        keep &= nv >= int(min_vertices)
+    if min_fraction is not None:
+        keep &= nv >= int(math.ceil(float(min_fraction) * V))
+    if keep_largest is not None:
+        # rank by vertex count descending, ties to the lower id: a stable sort
+        order = torch.sort(nv, descending=True, stable=True).indices
+        top = torch.zeros_like(keep)
+        top[order[:int(keep_largest)]] = True
+        keep &= top
+    return keep.to(torch.uint8).contiguous()
+
+
+@torch.no_grad()
+def filter_components(mesh, keep_largest=None, min_vertices=None, min_fraction=None):
+    """The Mesh of the components of `mesh` that meet every given criterion:
+    n_vertices[c] >= min_vertices; n_vertices[c] >= ceil(min_fraction * V);
+    rank below keep_largest, ranking by vertex count descending with ties to
+    the lower component id.  Kept vertices and faces keep their relative
+    order, face indices are remapped, normals and colors travel with their
+    vertices.  Labelling, counting and compaction run on the device; the call
+    synchronises twice in the usual case (components' flag read, then the kept
+    counts that size the outputs)."""
+    fn = "filter_components"
+    _criteria(fn, keep_largest, min_vertices, min_fraction)
+    comp, work = _components(fn, mesh)
+    V, F = mesh.vertices.shape[0], mesh.faces.shape[0]
+    dev = mesh.vertices.device
+    if V == 0:
+        return Mesh(mesh.vertices.clone(), mesh.faces.clone(),
+                    None if mesh.normals is None else mesh.normals.clone(),
+                    None if mesh.colors is None else mesh.colors.clone())
+    keep = _keep(comp, V, keep_largest, min_vertices, min_fraction)
+    C = keep.shape[0]
+    L, st = lib(), _stream(dev)
+    fp = mesh.faces.data_ptr() if F else None
+    L.mesh_compact_count(fp, F, V, comp.label.data_ptr(), keep.data_ptr(), C, work.data_ptr(), st)
+    n_v, n_f = work[24:40].view(torch.int64).tolist()              # sizes the outputs
+    v = torch.empty(n_v, 3, device=dev)
+    f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+    nr = None if mesh.normals is None else torch.empty(n_v, 3, device=dev)
+    col = None if mesh.colors is None else torch.empty(n_v, 3, dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.mesh_compact_emit(fp, F, V, work.data_ptr(), mesh.vertices.data_ptr(), ptr(mesh.normals),
+                        ptr(mesh.colors), n_v, n_f, ptr(v), ptr(nr), ptr(col), ptr(f), st)
+    return Mesh(v, f, nr, col)
+
+
 @torch.no_grad()
 def vertex_colors(model, vertices, normals, weights=None):
     """(V, 3) uint8: every live sub-NeRF's forward at the vertices, seen
@@ -322,14 +543,23 @@ def vertex_colors(model, vertices, normals, weights=None):
 
 @torch.no_grad()
 def extract_mesh(model, resolution=256, iso=None, aabb=None, weights=None, normals=True,
-                 colors=False):
-    """density_lattice, then surface_nets at the level iso (by default the
-    training density threshold DEFAULT_ISO, a choice), then with colors=True
-    vertex_colors (which takes the normals: they are computed either way)."""
-    sigma = density_lattice(model, resolution, aabb, weights)          # checks the arguments
+                 colors=False, occupancy=False, keep_largest=None, min_vertices=None,
+                 min_fraction=None):
+    """density_lattice (with occupancy=True masked by the occupancy bitfields:
+    see its caveat), then surface_nets at the level iso (by default the
+    training density threshold DEFAULT_ISO, a choice), then, if keep_largest,
+    min_vertices or min_fraction is given, filter_components, then with
+    colors=True vertex_colors on the vertices that are left (it takes the
+    normals: they are computed either way)."""
+    clean = not (keep_largest is None and min_vertices is None and min_fraction is None)
+    if clean:
+        _criteria("extract_mesh", keep_largest, min_vertices, min_fraction)
+    sigma = density_lattice(model, resolution, aabb, weights, occupancy=occupancy)
     mesh = surface_nets(sigma, DEFAULT_ISO if iso is None else iso,
                         _model_box(model) if aabb is None else aabb,
                         normals=normals or colors)
+    if clean:
+        mesh = filter_components(mesh, keep_largest, min_vertices, min_fraction)
     if colors and mesh.vertices.shape[0]:
         mesh.colors = vertex_colors(model, mesh.vertices, mesh.normals, weights)
     elif colors:

@@ -703,7 +703,8 @@ class Trainer:
 
     def export_mesh(self, path, **kw):
         """The model's iso-surface as a .ply / .obj file (mesh.extract_mesh's
-        arguments: resolution, iso, aabb, weights, normals, colors); returns the
+        arguments: resolution, iso, aabb, weights, normals, colors, and for the
+        clean-up occupancy, keep_largest, min_vertices, min_fraction); returns the
         Mesh.  Reads the model only: parameters, grids and the optimiser's state
         are left as they are."""
         from .mesh import extract_mesh

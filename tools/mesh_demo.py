@@ -6,8 +6,12 @@ exports the geometry at 128^3 with the default level (the training density
 threshold) and reports, for the mean of the sub-NeRFs and for each sub-NeRF
 alone (one-hot weights): V, F, the Euler characteristic, the number of
 connected components, and for the largest component its share of the vertices
-and its radius error max|r - 0.25|.  Whatever floats beside the sphere is in
-the counts: nothing is filtered.
+and its radius error max|r - 0.25|, and over all used vertices the mean radius
+and the worst vertex.  The first export filters nothing: whatever floats
+beside the sphere is in the counts.  Then the same model is exported with the
+occupancy mask alone (occupancy=True) and with the mask and the component
+filter (occupancy=True, keep_largest=1), whose one derivable bar is exactly
+one component (counted on the device by mesh.components).
 
     python tools/mesh_demo.py [steps] [rays] [resolution] [--out FILE] [--ply FILE]
 """
@@ -53,6 +57,9 @@ def describe(mesh):
     ids, counts = np.unique(lab, return_counts=True)
     big = used[lab == ids[np.argmax(counts)]]
     r = np.linalg.norm(v[big], axis=1)
+    ra = np.linalg.norm(v[used], axis=1)
+    out.update({"radius_mean_all": round(float(ra.mean()), 5),
+                "worst_vertex_err": round(float(np.abs(ra - R_SPHERE).max()), 5)})
     # per-component Euler characteristic of the largest one
     fb = f[np.isin(f[:, 0], big)]
     eb = np.unique(np.sort(np.concatenate([fb[:, [0, 1]], fb[:, [1, 2]], fb[:, [2, 0]]]), 1), axis=0)
@@ -112,7 +119,12 @@ def main():
     for k in range(K):
         w = [1.0 if q == k else 0.0 for q in range(K)]
         rec[f"sub_nerf_{k}"] = describe(mesh.extract_mesh(m, resolution=res, weights=w))
-    append_jsonl(opt("--out", os.path.join(ROOT, "profiles", "mesh", "mesh_demo.jsonl")), rec)
+    rec["masked"] = describe(mesh.extract_mesh(m, resolution=res, occupancy=True))
+    clean = mesh.extract_mesh(m, resolution=res, occupancy=True, keep_largest=1)
+    rec["masked_largest"] = describe(clean)
+    rec["masked_largest"]["device_components"] = int(mesh.components(clean).n_vertices.shape[0])
+    rec["unmasked_largest"] = describe(mesh.extract_mesh(m, resolution=res, keep_largest=1))
+    append_jsonl(opt("--out", os.path.join(ROOT, "profiles", "mesh_clean", "mesh_demo.jsonl")), rec)
 
 
 if __name__ == "__main__":
