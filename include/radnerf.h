@@ -1204,6 +1204,89 @@ int rn_mesh_compact_emit(const int32_t* faces, int64_t n_faces, int64_t n_vertic
                          float* out_vertices, float* out_normals, uint8_t* out_colors,
                          int32_t* out_faces, void* stream);
 
+/* ---- TSDF fusion (tsdf.hip, mesh.hip; radnerf_amd/tsdf.py) -------------------
+ * Rendered depth images folded into a truncated signed distance volume on a
+ * lattice (geometry as rn_density_lattice: nx x ny x nz cells, x fastest, point
+ * i of an axis at lo + (float)i * step), the surface nets of such a volume, and
+ * vertex colours from it.  No entry synchronises with the host or uses an
+ * atomic; invalid arguments give status 1 and nothing is written.
+ * Volume state per point: phi (points) fp32, the mean of the truncated signed
+ * distances observed, POSITIVE INSIDE, in units of trunc (so in [-1, 1]); w
+ * (points) fp32, the integer-valued number of observations; optionally vol_rgb
+ * (points, 3) fp32 and wc (points) fp32, the mean colour and its count (both
+ * or neither).  A fresh volume is all zeros; w == 0 means "never observed".
+ * rn_tsdf_integrate: one launch folds n_cams depth images into the volume.
+ * poses (n_cams, 3, 4) c2w on the device, axes right / down / front, R[i][j] =
+ * pose[4 i + j], T_i = pose[4 i + 3]; one pinhole fx, fy, cx, cy, width x
+ * height for all (pixel centres at +0.5, as ray_utils.py:8-42); directions
+ * (width * height, 3), the buffer the images were rendered with (it need not
+ * be normalised); depth, opacity (n_cams, width * height), the renderer's
+ * sum w t and sum w; rgb (n_cams, width * height, 3) or NULL (then vol_rgb and
+ * wc are left alone; rgb needs vol_rgb).  trunc > 0, near_distance >= 0,
+ * opacity_min > 0.  n_cams == 0 is a valid no-op.
+ * The operation order is part of the interface.  Everything is fp32, every
+ * operation rounded on its own (no fused multiply-add; divisions and square
+ * roots correctly rounded).  The point at X_a = lo_a + (float)i_a * step_a
+ * visits the cameras c = 0 .. n_cams - 1 in that order; with d_j = X_j - T_j:
+ *   xc = (R[0][0]*d_0 + R[1][0]*d_1) + R[2][0]*d_2
+ *   yc, zc: the same with column 1, column 2 of R (as rn_mark_invisible_cells)
+ *   next camera unless zc >= near_distance
+ *   px = (fx*xc)/zc + cx;  py = (fy*yc)/zc + cy;  u = floorf(px), v = floorf(py)
+ *   next camera unless 0 <= u < width and 0 <= v < height (compared as floats:
+ *   a NaN is outside);  pix = v * width + u
+ *   o = opacity[c][pix]
+ *   unless o >= opacity_min (a miss; a NaN too):
+ *     carve == 0: next camera;  carve != 0: phi_obs = -1, no colour (free space)
+ *   else:
+ *     d  = depth[c][pix] / o
+ *     e  = directions[pix];  n2 = (e_0*e_0 + e_1*e_1) + e_2*e_2
+ *     tv = ((xc*e_0 + yc*e_1) + zc*e_2) / n2
+ *     s  = (tv - d) * sqrtf(n2)       (world distance behind the surface)
+ *     next camera unless s <= trunc   (hidden: not observed; a NaN too)
+ *     phi_obs = fmaxf(s / trunc, -1);  colour iff s >= -trunc
+ *   phi = (phi * w + phi_obs) / (w + 1);  w = w + 1
+ *   with rgb and colour, per channel k: vol_rgb_k = (vol_rgb_k * wc +
+ *   rgb[c][pix][k]) / (wc + 1);  then wc = wc + 1
+ * The point's state is read once before and written once after its cameras
+ * (not at all where no camera observed it), so any split of the cameras into
+ * consecutive launches gives the same bits as one launch.
+ * rn_surface_count_valid / rn_surface_emit_valid: rn_surface_count /
+ * rn_surface_emit on the lattice phi with the observation counts w, and two
+ * more rules: a cell is active only if all 8 of its corners have w > 0 (and
+ * are not all alike); a lattice edge emits its quad only if, besides
+ * rn_surface_count's conditions, all four cells around it have all corners
+ * observed.  Inside, positions, normals, the two orders, work
+ * (rn_surface_work_bytes, the same layout) and the counts in work[0], work[1]
+ * are rn_surface_*'s; with w > 0 everywhere the output has rn_surface_*'s
+ * bits.  rn_surface_emit_valid reads the classification from work (and the
+ * values of active cells only); w must be the lattice rn_surface_count_valid
+ * classified.
+ * rn_lattice_colors: colors (n_vertices, 3) uint8 from the colour lattice.
+ * Per vertex and axis a (n_a cells): g = (v_a - lo_a) / step_a (a division),
+ * c = fminf(fmaxf(floorf(g), 0), n_a - 1) (NaN gives 0), f = fminf(fmaxf(g -
+ * c, 0), 1); corner q = 0 .. 7 of cell c at offset (q & 1, q >> 1 & 1, q >> 2
+ * & 1) has the weight t_q = (wx * wy) * wz with w_a = f_a where the offset is
+ * 1, else 1 - f_a.  Over the corners with wc > 0, q ascending: sw = sw + t_q,
+ * acc_k = acc_k + t_q * vol_rgb[corner][k].  Channel k is acc_k / sw, or 0
+ * when sw is not positive, quantised by rn_quantize_u8's rule (times 255.0f,
+ * NaN -> 0, clamped to [0, 255], truncated).  n_vertices == 0 is a valid
+ * no-op.                                                                      */
+int rn_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, const float* lo, const float* step,
+                      const float* poses, int32_t n_cams, float fx, float fy, float cx, float cy,
+                      int32_t width, int32_t height, const float* directions, const float* depth,
+                      const float* opacity, const float* rgb, float trunc, float near_distance,
+                      float opacity_min, int32_t carve, float* phi, float* w, float* vol_rgb,
+                      float* wc, void* stream);
+int rn_surface_count_valid(const float* phi, const float* w, int32_t nx, int32_t ny, int32_t nz,
+                           float iso, void* work, void* stream);
+int rn_surface_emit_valid(const float* phi, const float* w, int32_t nx, int32_t ny, int32_t nz,
+                          float iso, const float* lo, const float* step, const void* work,
+                          int64_t n_vertices, int64_t n_quads, float* vertices, float* normals,
+                          int32_t* faces, void* stream);
+int rn_lattice_colors(const float* vertices, int64_t n_vertices, int32_t nx, int32_t ny,
+                      int32_t nz, const float* lo, const float* step, const float* vol_rgb,
+                      const float* wc, uint8_t* colors, void* stream);
+
 /* ---- LPIPS (VGG) (train_ml.py:64-70, --eval_lpips) --------------------------
  * The pieces of the LPIPS distance of the `lpips` package 0.1, net vgg: the
  * input step, VGG16's 3 x 3 convolutions, its 2 x 2 max-pool and the per-tap

@@ -211,6 +211,7 @@ k_density_lattice_masked(FieldArgs a, LatticeArgs g, MaskArgs m) {
 // ---------------------------------------------------------------------------
 struct SurfArgs {
     const float* s;
+    const float* w;                // rn_surface_count_valid: the observation counts, else null
     uint32_t nx, ny, nz, px, py;   // cells per axis; points per row / column
     uint32_t n_pts, nb;
     float iso;
@@ -244,8 +245,27 @@ __device__ __forceinline__ void sn_corners(const SurfArgs& u, uint32_t pi, uint3
     }
 }
 
+// VALID: every corner of the cell at (pi, pj, pk) is observed (w > 0; NaN is
+// not).  A cell past the lattice clamps as sn_corners does: it is never active.
+__device__ __forceinline__ bool sn_cell_valid(const SurfArgs& u, uint32_t pi, uint32_t pj,
+                                              uint32_t pk) {
+    const uint32_t x1 = min(pi + 1, u.nx), y1 = min(pj + 1, u.ny), z1 = min(pk + 1, u.nz);
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const uint32_t x = (q & 1) ? x1 : pi, y = (q & 2) ? y1 : pj, z = (q & 4) ? z1 : pk;
+        ok &= u.w[x + u.px * (y + u.py * z)] > 0.f;
+    }
+    return ok;
+}
+
 // 1. classify every lattice point: is its cell active, which of its three
-// edges emit a quad; per chunk the ballots, per block the counts
+// edges emit a quad; per chunk the ballots, per block the counts.  VALID
+// (rn_surface_count_valid): a cell with an unobserved corner is not active, an
+// edge with such a cell among its four emits nothing; the four cells of an
+// interior edge lie inside the lattice, and the branch runs only at a sign
+// change.  Every other line is the same code for both.
+template <bool VALID>
 __global__ void __launch_bounds__(256)
 k_sn_classify(SurfArgs u) {
     __shared__ int sCnt[SN_CHUNKS][2];
@@ -265,11 +285,20 @@ k_sn_classify(SurfArgs u) {
             for (int q = 0; q < 8; ++q) { in[q] = sn_inside(v[q], u.iso); any |= in[q]; all &= in[q]; }
             const uint32_t n[3] = {u.nx, u.ny, u.nz};
             cell = P[0] < n[0] && P[1] < n[1] && P[2] < n[2] && any && !all;
+            if (VALID && cell) cell = sn_cell_valid(u, P[0], P[1], P[2]);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 const int bb = (a + 1) % 3, cc = (a + 2) % 3;
                 qa[a] = in[0] != in[1 << a] && P[a] < n[a] && P[bb] >= 1 && P[bb] < n[bb] &&
                         P[cc] >= 1 && P[cc] < n[cc];
+                if (VALID && qa[a]) {
+                    uint32_t Q[3] = {P[0], P[1], P[2]};
+                    bool ok = sn_cell_valid(u, Q[0], Q[1], Q[2]);
+                    Q[bb] -= 1; ok = ok && sn_cell_valid(u, Q[0], Q[1], Q[2]);
+                    Q[cc] -= 1; ok = ok && sn_cell_valid(u, Q[0], Q[1], Q[2]);
+                    Q[bb] += 1; ok = ok && sn_cell_valid(u, Q[0], Q[1], Q[2]);
+                    qa[a] = ok;
+                }
             }
         }
         const uint64_t m0 = __ballot(cell), m1 = __ballot(qa[0]), m2 = __ballot(qa[1]),
@@ -482,6 +511,26 @@ int lattice_launch(const char* who, int32_t nx, int32_t ny, int32_t nz, const fl
     return 0;
 }
 
+// both emit entries
+int emit_launch(const char* who, const float* sigma, int32_t nx, int32_t ny, int32_t nz, float iso,
+                const float* lo, const float* step, const void* work, int64_t n_vertices,
+                int64_t n_quads, float* vertices, float* normals, int32_t* faces, void* stream) {
+    RN_CHECK_ARG_AS(who, sigma && work && lo && step, "null pointer");
+    RN_CHECK_ARG_AS(who, n_vertices >= 0 && n_quads >= 0 && n_vertices < ((int64_t)1 << 31) &&
+                    2 * n_quads < ((int64_t)1 << 31), "bad counts (vertices, triangles < 2^31)");
+    RN_CHECK_ARG_AS(who, (n_vertices == 0 || vertices) && (n_quads == 0 || faces), "null output");
+    SurfArgs u{};
+    if (sn_fill(u, who, sigma, nx, ny, nz, const_cast<void*>(work))) return 1;
+    u.iso = iso;
+    for (int d = 0; d < 3; ++d) { u.lo[d] = lo[d]; u.step[d] = step[d]; }
+    u.cap_v = n_vertices; u.cap_q = n_quads;
+    u.vertices = vertices; u.normals = normals; u.faces = faces;
+    if (n_vertices == 0 && n_quads == 0) return 0;
+    k_sn_emit<<<u.nb, 256, 0, (hipStream_t)stream>>>(u);
+    RN_CHECK_LAUNCH_AS(who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -525,7 +574,21 @@ int rn_surface_count(const float* sigma, int32_t nx, int32_t ny, int32_t nz, flo
     if (sn_fill(u, __func__, sigma, nx, ny, nz, work)) return 1;
     u.iso = iso;
     hipStream_t st = (hipStream_t)stream;
-    k_sn_classify<<<u.nb, 256, 0, st>>>(u);
+    k_sn_classify<false><<<u.nb, 256, 0, st>>>(u);
+    k_sn_scan<<<2, 1024, 0, st>>>(u);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_surface_count_valid(const float* phi, const float* w, int32_t nx, int32_t ny, int32_t nz,
+                           float iso, void* work, void* stream) {
+    RN_CHECK_ARG(phi && w && work, "null pointer");
+    SurfArgs u{};
+    if (sn_fill(u, __func__, phi, nx, ny, nz, work)) return 1;
+    u.w = w;
+    u.iso = iso;
+    hipStream_t st = (hipStream_t)stream;
+    k_sn_classify<true><<<u.nb, 256, 0, st>>>(u);
     k_sn_scan<<<2, 1024, 0, st>>>(u);
     RN_CHECK_LAUNCH();
     return 0;
@@ -535,20 +598,19 @@ int rn_surface_emit(const float* sigma, int32_t nx, int32_t ny, int32_t nz, floa
                     const float* lo, const float* step, const void* work, int64_t n_vertices,
                     int64_t n_quads, float* vertices, float* normals, int32_t* faces,
                     void* stream) {
-    RN_CHECK_ARG(sigma && work && lo && step, "null pointer");
-    RN_CHECK_ARG(n_vertices >= 0 && n_quads >= 0 && n_vertices < ((int64_t)1 << 31) &&
-                 2 * n_quads < ((int64_t)1 << 31), "bad counts (vertices, triangles < 2^31)");
-    RN_CHECK_ARG((n_vertices == 0 || vertices) && (n_quads == 0 || faces), "null output");
-    SurfArgs u{};
-    if (sn_fill(u, __func__, sigma, nx, ny, nz, const_cast<void*>(work))) return 1;
-    u.iso = iso;
-    for (int d = 0; d < 3; ++d) { u.lo[d] = lo[d]; u.step[d] = step[d]; }
-    u.cap_v = n_vertices; u.cap_q = n_quads;
-    u.vertices = vertices; u.normals = normals; u.faces = faces;
-    if (n_vertices == 0 && n_quads == 0) return 0;
-    k_sn_emit<<<u.nb, 256, 0, (hipStream_t)stream>>>(u);
-    RN_CHECK_LAUNCH();
-    return 0;
+    return emit_launch(__func__, sigma, nx, ny, nz, iso, lo, step, work, n_vertices, n_quads,
+                       vertices, normals, faces, stream);
+}
+
+int rn_surface_emit_valid(const float* phi, const float* w, int32_t nx, int32_t ny, int32_t nz,
+                          float iso, const float* lo, const float* step, const void* work,
+                          int64_t n_vertices, int64_t n_quads, float* vertices, float* normals,
+                          int32_t* faces, void* stream) {
+    // the classification in work carries the observation rules: the emit reads
+    // the ballots and the values of active cells, all of whose corners are observed
+    RN_CHECK_ARG(w, "null pointer");
+    return emit_launch(__func__, phi, nx, ny, nz, iso, lo, step, work, n_vertices, n_quads,
+                       vertices, normals, faces, stream);
 }
 
 }  // extern "C"

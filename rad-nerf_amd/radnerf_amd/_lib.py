@@ -149,6 +149,12 @@ SIGNATURES = {
     "rn_mesh_components": [P, I64, I64, P, P, I64, P, P, P, P],
     "rn_mesh_compact_count": [P, I64, I64, P, P, I64, P, P],
     "rn_mesh_compact_emit": [P, I64, I64, P, P, P, P, I64, I64, P, P, P, P, P],
+    # TSDF fusion (tsdf.TSDFVolume, tsdf.fuse_mesh)
+    "rn_tsdf_integrate": [I32, I32, I32, P, P, P, I32, F32, F32, F32, F32, I32, I32, P, P, P, P,
+                          F32, F32, F32, I32, P, P, P, P, P],
+    "rn_surface_count_valid": [P, P, I32, I32, I32, F32, P, P],
+    "rn_surface_emit_valid": [P, P, I32, I32, I32, F32, P, P, P, I64, I64, P, P, P, P],
+    "rn_lattice_colors": [P, I64, I32, I32, I32, P, P, P, P, P, P],
     # LPIPS (VGG) (lpips.LPIPS)
     "rn_lpips_prepare": [P, I64, P, P],
     "rn_conv3x3_relu_f16": [P, P, P, I32, I32, I32, I32, I32, P, P],

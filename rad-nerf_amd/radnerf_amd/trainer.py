@@ -231,6 +231,8 @@ class Trainer:
         self.n_rays, self.lr0 = int(n_rays), float(lr)
         # validate()'s camera: (W, H) of `directions`
         self.img_wh = None if img_wh is None else (int(img_wh[0]), int(img_wh[1]))
+        # the 3x3 pinhole of `directions` (cull_invisible, export_mesh(method="tsdf"))
+        self.intrinsics = intrinsics
         self._evaluator = None
         self.model, self.gate = model, gating_net
         self.device = model.mlp_params.device
@@ -701,14 +703,45 @@ class Trainer:
             for k, v in poses.items():
                 getattr(self, k).copy_(v.to(self.device, torch.float32))
 
-    def export_mesh(self, path, **kw):
-        """The model's iso-surface as a .ply / .obj file (mesh.extract_mesh's
-        arguments: resolution, iso, aabb, weights, normals, colors, and for the
-        clean-up occupancy, keep_largest, min_vertices, min_fraction); returns the
-        Mesh.  Reads the model only: parameters, grids and the optimiser's state
-        are left as they are."""
-        from .mesh import extract_mesh
-        mesh = extract_mesh(self.model, **kw)
+    def export_mesh(self, path, method="density", poses=None, **kw):
+        """The model's surface as a .ply / .obj file; returns the Mesh.  Reads
+        the model only: parameters, grids and the optimiser's state are left as
+        they are.
+        method="density" (the default): the iso-surface of the density lattice
+        (mesh.extract_mesh's arguments: resolution, iso, aabb, weights, normals,
+        colors, and for the clean-up occupancy, keep_largest, min_vertices,
+        min_fraction).
+        method="tsdf": what the model renders, fused from depth images
+        (tsdf.fuse_mesh's arguments) of this trainer's camera -- directions,
+        img_wh, intrinsics -- from `poses` ((N, 3, 4); None: the training
+        poses, as given, without dR / dT), rendered with this trainer's
+        `routing` and exp_step_factor unless kw overrides them.  ValueError
+        naming what is missing when the trainer was built without directions /
+        poses, img_wh or intrinsics."""
+        if method == "density":
+            if poses is not None:
+                raise ValueError("Trainer.export_mesh: poses belong to method=\"tsdf\"; the "
+                                 "density method renders nothing")
+            from .mesh import extract_mesh
+            mesh = extract_mesh(self.model, **kw)
+        elif method == "tsdf":
+            missing = [name for name, v in (("directions", self.directions),
+                                            ("img_wh", self.img_wh),
+                                            ("intrinsics", self.intrinsics)) if v is None]
+            if poses is None and self.poses is None:
+                missing.append("poses")
+            if missing:
+                raise ValueError("Trainer.export_mesh(method=\"tsdf\") needs Trainer("
+                                 + ", ".join(f"{m}=..." for m in missing) + "): the depth "
+                                 "images are rendered from those cameras")
+            from .tsdf import fuse_mesh
+            args = dict(self.routing, exp_step_factor=self.esf)
+            args.update(kw)
+            mesh = fuse_mesh(self.model, self.gate, self.poses if poses is None else poses,
+                             self.directions, self.img_wh, self.intrinsics, **args)
+        else:
+            raise ValueError(f"Trainer.export_mesh: method must be \"density\" or \"tsdf\", got "
+                             f"{method!r}")
         mesh.save(path)
         return mesh
 
