@@ -196,6 +196,45 @@ int rn_ml_composite_dist_bw(const float* dL_drgb, const float* dL_dopacity,
                             const float* opacity_k, const float* depth_k, const float* rgb_k,
                             const float* dist_k, int64_t n_rays, int32_t n_models,
                             float T_threshold, float* dL_dsigmas, float* dL_drgbs, void* stream);
+/* the same with depth supervision's ray-termination term in the chain: per
+ * (model k, ray r) segment the second moment of its weights about the ray's
+ * target ray parameter z = target_t[r] ((B) fp32; z <= 0: no measurement),
+ *   dvar_k[k][r] = sum over the live samples s (up to the termination sample,
+ *                  where ws != 0 can hold) of w_s min((t_s - z)^2, clip^2),
+ * exactly 0 for z <= 0 and for an empty segment.  clip > 0 (INFINITY: none);
+ * clip2 = clip * clip is one fp32 multiply on the host.
+ * fw, per lane over its samples in ascending order (fp32, no contraction):
+ *   e = t - z;  phi = fminf(e * e, clip2);  acc = fmaf(w, phi, acc)
+ *   then one butterfly sum over the 64 lanes, as for depth_k.  dist_k NULL:
+ *   every other output is rn_ml_composite_fw's, bit for bit; dist_k given: it
+ *   and every other output are rn_ml_composite_dist_fw's, bit for bit.
+ * bw, for the seed gv = dL_ddvar[k][r] ([K][B]): the per-sample seed on w_s is
+ *   gw_s = gv * phi_s (phi as above; 0 for z <= 0 and past the termination) and
+ *   the segment total of gw w is gv * dvar_k[k][r]; both enter
+ *   dL/dsigma_s = delta_s [T_{s+1} gw_s - (total - sum_{j<=s} gw_j w_j)] + the
+ *   plain terms, the expression rn_composite_train_bw evaluates for dL_dws; w is
+ *   recomputed, ws is not read.  With dist_k and ws given (both or neither;
+ *   dL_ddist [K][B] or NULL for the constant dL_ddist_const) the distortion
+ *   seed joins as in rn_ml_composite_dist_bw: gw_s = gw_dist_s + gv * phi_s and
+ *   total = 2 g dist_k + gv * dvar_k, added in that order.  No gradient reaches
+ *   ts, deltas or target_t.                                                   */
+int rn_ml_composite_depth_fw(const float* sigmas, const float* rgbs, const float* deltas,
+                             const float* ts, const int32_t* counts, const int32_t* offsets,
+                             int64_t n_rays, int32_t n_models, float T_threshold, int32_t* used,
+                             float* opacity_k, float* depth_k, float* rgb_k, float* ws,
+                             const float* target_t, float clip, float* dist_k /*may be NULL*/,
+                             float* dvar_k, void* stream);
+int rn_ml_composite_depth_bw(const float* dL_drgb, const float* dL_dopacity,
+                             const float* dL_ddepth, const float* gate, const float* bg,
+                             const float* sigmas, const float* rgbs, const float* deltas,
+                             const float* ts, const int32_t* counts, const int32_t* offsets,
+                             const float* opacity_k, const float* depth_k, const float* rgb_k,
+                             const float* target_t, float clip, const float* dL_ddvar,
+                             const float* dvar_k, const float* dL_ddist /*may be NULL*/,
+                             float dL_ddist_const, const float* ws /*may be NULL*/,
+                             const float* dist_k /*may be NULL*/, int64_t n_rays,
+                             int32_t n_models, float T_threshold, float* dL_dsigmas,
+                             float* dL_drgbs, void* stream);
 
 /* ---- field: shared hash grid + per-model geo/rgb MLP -----------------------
  * replaces MNGP.forward / tcnn Encoding+Network fwd/bwd
@@ -931,6 +970,51 @@ int rn_guided_epilogue(const float* rgb, const float* target_rgb, const int32_t*
                        float* dL_ddepth /*may be NULL*/, void* stream);
 int rn_guided_refresh(float* emap, uint64_t* acc_sum, uint32_t* acc_cnt, int64_t n_cells,
                       float alpha, void* stream);
+
+/* ---- depth supervision --------------------------------------------------------
+ * rn_gather_depth: the target ray parameter of each pick of a batch, one thread
+ * per ray, after the picks exist (rn_sample_batch*, or the caller's).  depths:
+ * (n_images, n_pix) on the device, uint16 (depth_dtype 0) or fp32 (1); the
+ * element offset img n_pix + pix is 64-bit.  With v the raw value as fp32:
+ *   kind 0: t = v * scale, one fp32 multiply (the z-depth of a camera whose
+ *           directions have z = 1 and are not normalised, ray_utils.py:45-70);
+ *   kind 1: Euclidean range: t = (v * scale) / sqrtf((dx dx + dy dy) + dz dz)
+ *           with d = directions[pix] ((n_pix, 3), may be NULL for kind 0), the
+ *           square root and the division correctly rounded, no contraction.
+ * target_t[r] = t when v > 0 and t > 0, else 0 (a raw 0, a negative value, a
+ * NaN, a pick outside the maps): 0 means "no measurement" downstream.  Status
+ * 1: n_images or n_pix outside [1, 2^32), a dtype or kind other than 0 / 1, a
+ * missing pointer.  n_rays == 0 is a no-op.
+ *
+ * rn_depth_loss: the two depth terms and their seeds, after rn_nerf_loss* and
+ * rn_guided_epilogue (it adds into their seeds).  depth, gate (n_rays,
+ * n_models): the render's per-model depth and the gate it was combined with
+ * (gate_used on a routed step); dvar_k [K][B] (rn_ml_composite_depth_fw) or
+ * NULL together with dL_ddvar (mean term only); z = target_t[r], m = z > 0;
+ * rw = ray_weight[r], or 1 when ray_weight is NULL; B = n_rays.  Per ray with
+ * m (fp32, no contraction, k ascending):
+ *   lambda_depth > 0:  mean = sum_k gate[r,k] * depth[r,k];  e = mean - z;
+ *     l0 = lambda_depth * (e * e);  s = ((2 lambda_depth / B) * e) * rw;
+ *     dL_ddepth[r,k] += s * gate[r,k];  dL_dgate[r,k] += s * depth[r,k]
+ *   dvar_k given:  l1 = lambda_depth_var * sum_k gate[r,k] * dvar_k[k][r];
+ *     s = (lambda_depth_var / B) * rw (0 without m or with lambda_depth_var
+ *     <= 0);  dL_ddvar[k][r] = s * gate[r,k] (written, every ray);
+ *     dL_dgate[r,k] += s * dvar_k[k][r]
+ * A ray without m adds nothing and gets dL_ddvar = 0.  loss_out[0] = sum l0,
+ * loss_out[1] = sum l1 (the caller divides by B; the terms carry no
+ * ray_weight), always as ordered sums: per-block partials into part
+ * ([ceil(n_rays / 256)][2] fp32; a fixed xor butterfly per wave, then the four
+ * waves in order), added in block order by one thread per term, so two calls
+ * give the same bits.                                                         */
+int rn_gather_depth(const void* depths, int32_t depth_dtype, int64_t n_images, int64_t n_pix,
+                    float scale, int32_t kind, const float* directions /*may be NULL*/,
+                    const int64_t* img_idxs, const int64_t* pix_idxs, int64_t n_rays,
+                    float* target_t, void* stream);
+int rn_depth_loss(const float* depth, const float* gate, const float* dvar_k /*may be NULL*/,
+                  const float* target_t, const float* ray_weight /*may be NULL*/, int64_t n_rays,
+                  int32_t n_models, float lambda_depth, float lambda_depth_var, float* loss_out,
+                  float* part, float* dL_ddepth, float* dL_dgate, float* dL_ddvar /*may be NULL*/,
+                  void* stream);
 
 /* ---- whole-image validation (train_ml.py:214-250) ---------------------------
  * rn_ml_combine_test: the test-time epilogue of ml_rendering.py:65-68,149-153

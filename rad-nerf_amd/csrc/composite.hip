@@ -38,15 +38,21 @@ __device__ __forceinline__ int seg_break(const float* __restrict__ sig,
 // of non-negative products; t is taken relative to the segment's first
 // sample (the loss is translation invariant), which removes the cancellation
 // of the absolute-t scans.  Every other output is the plain instantiation's.
-template <bool DIST>
+// DEPTH: also the segment's ray-termination second moment about the target z,
+// *dvar = sum over the live samples of w min((t - z)^2, clip2), per lane
+// e = t - z; phi = fminf(e * e, clip2); aV = fmaf(w, phi, aV) in sample order,
+// one rn_wave_sum at the end; z <= 0 (no measurement) adds nothing: exactly 0.
+template <bool DIST, bool DEPTH = false>
 __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __restrict__ rgbs,
                               const float* __restrict__ dl, const float* __restrict__ ts,
                               int64_t start, int n, float thr, float* __restrict__ ws,
-                              float* __restrict__ dist = nullptr) {
+                              float* __restrict__ dist = nullptr, float z = 0.f,
+                              float clip2 = 0.f, float* __restrict__ dvar = nullptr) {
     const int lane = rn_lane();
     float T = 1.0f;
     float aO = 0.f, aD = 0.f, aR = 0.f, aG = 0.f, aB = 0.f;
-    float t0 = 0.f, pw = 0.f, pwt = 0.f, aL = 0.f;
+    float t0 = 0.f, pw = 0.f, pwt = 0.f, aL = 0.f, aV = 0.f;
+    const bool zpos = DEPTH && z > 0.f;
     if (DIST && n > 0) t0 = ts[start];
     int used = n;
     bool done = false;
@@ -82,6 +88,12 @@ __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __rest
             aR = fmaf(w, c0, aR); aG = fmaf(w, c1, aG); aB = fmaf(w, c2, aB);
             aD = fmaf(w, t, aD); aO += w;
         }
+        if (DEPTH) {
+            if (live && zpos) {
+                const float e = t - z;
+                aV = fmaf(w, fminf(e * e, clip2), aV);
+            }
+        }
         if (DIST) {
             const float wl = live ? w : 0.f, tr = t - t0;
             const float sw = pw + rn_wave_incl_sum(wl);
@@ -96,6 +108,10 @@ __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __rest
     if (DIST) {
         aL = rn_wave_sum(aL);
         if (lane == 0) *dist = aL;
+    }
+    if (DEPTH) {
+        aV = rn_wave_sum(aV);
+        if (lane == 0) *dvar = aV;
     }
     SegOut o;
     o.O = rn_wave_sum(aO); o.D = rn_wave_sum(aD);
@@ -113,14 +129,19 @@ __device__ SegOut seg_forward(const float* __restrict__ sig, const float* __rest
 // loop's own scan order (so total - inclusive is exactly 0 at the last
 // sample).  The loss is homogeneous of degree 2 in ws, so the total of
 // dL_dws * ws (the thrust scan's last element) is 2 g dist.
-template <bool DIST>
+// DEPTH: the seed gv on the segment's second moment dvar (seg_forward) adds
+// gw_s = gv min((t_s - z)^2, clip2) per live sample (0 for z <= 0) and gv dvar
+// to the total; the loss is linear in ws, so nothing else is needed.  Without
+// DIST neither ws nor dL_dws is read: w is recomputed, as in the plain kernel.
+template <bool DIST, bool DEPTH = false>
 __device__ void seg_backward(const float* __restrict__ sig, const float* __restrict__ rgbs,
                              const float* __restrict__ dl, const float* __restrict__ ts,
                              const float* __restrict__ ws, const float* __restrict__ dL_dws,
                              int64_t start, int n, float thr, float R, float G, float B, float O,
                              float D, float gR, float gG, float gB, float gO, float gD,
                              float* __restrict__ dsig, float* __restrict__ drgb, float g = 0.f,
-                             float dist = 0.f) {
+                             float dist = 0.f, float z = 0.f, float clip2 = 0.f, float gv = 0.f,
+                             float dvar = 0.f) {
     const int lane = rn_lane();
     // total of dL_dws*ws over the whole segment (thrust scan's last element)
     float wsum_part = 0.f;
@@ -140,7 +161,10 @@ __device__ void seg_backward(const float* __restrict__ sig, const float* __restr
             if (i < n) wsum_part += dL_dws[start + i] * ws[start + i];
         }
     }
-    const float wtot = DIST ? 2.0f * g * dist : (dL_dws ? rn_wave_sum(wsum_part) : 0.f);
+    float wtot_ = DIST ? 2.0f * g * dist : (dL_dws ? rn_wave_sum(wsum_part) : 0.f);
+    if (DEPTH) wtot_ = DIST ? wtot_ + gv * dvar : gv * dvar;
+    const float wtot = wtot_;
+    const bool zpos = DEPTH && z > 0.f;
     const float gterm_O = gO * (1 - O);
     float T = 1.0f, pr = 0.f, pg = 0.f, pb = 0.f, pd = 0.f, pw = 0.f;
     bool done = false;
@@ -179,6 +203,16 @@ __device__ void seg_backward(const float* __restrict__ sig, const float* __restr
             gw = (g * 2 * (front + back) + g * (2.0f / 3) * wsv * d) + 0.0f;
             qw = rn_wave_last(W_in);
             qwt = rn_wave_last(WT_in);
+        }
+        if (DEPTH) {
+            const float e = t - z;
+            const float gp = (live && zpos) ? gv * fminf(e * e, clip2) : 0.f;
+            if (DIST) {
+                gw = gw + gp;
+            } else {
+                wsv = live ? w : 0.f;
+                gw = gp;
+            }
         }
         // inclusive prefix sums (r, g, b, d accumulate before the gradient)
         const float sr = pr + rn_wave_incl_sum(live ? w * c0 : 0.f);
@@ -316,6 +350,31 @@ k_ml_composite_dist_fw(int n_rays, int K, const float* __restrict__ sig,
     }
 }
 
+// the same, plus the per-segment second moment about the ray's target
+// dvar_k[K][B] (rn_ml_composite_depth_fw); DIST: and dist_k as above
+template <bool DIST>
+__global__ void __launch_bounds__(256)
+k_ml_composite_depth_fw(int n_rays, int K, const float* __restrict__ sig,
+                        const float* __restrict__ rgbs, const float* __restrict__ dl,
+                        const float* __restrict__ ts, const int32_t* __restrict__ counts,
+                        const int32_t* __restrict__ offsets, float thr,
+                        int32_t* __restrict__ used, float* __restrict__ Ok,
+                        float* __restrict__ Dk, float* __restrict__ RGBk, float* __restrict__ ws,
+                        const float* __restrict__ target_t, float clip2,
+                        float* __restrict__ dist_k, float* __restrict__ dvar_k) {
+    const int seg = blockIdx.x * (blockDim.x / RN_WAVE) + (threadIdx.x / RN_WAVE);
+    if (seg >= n_rays * K) return;
+    const int k = seg / n_rays, r = seg - k * n_rays;
+    SegOut o = seg_forward<DIST, true>(sig, rgbs, dl, ts, offsets[seg], counts[seg], thr, ws,
+                                       DIST ? dist_k + seg : nullptr, target_t[r], clip2,
+                                       dvar_k + seg);
+    if (rn_lane() == 0) {
+        used[seg] = o.used;
+        Ok[seg] = o.O; Dk[seg] = o.D;
+        RGBk[3 * seg] = o.R; RGBk[3 * seg + 1] = o.G; RGBk[3 * seg + 2] = o.B;
+    }
+}
+
 // ml_rendering.py:66-68 (+ bg at :192-200), thread per ray, same op order as
 // the reference's torch ops:  rgb_i = rgb_i + bg*(1-O_i);  acc = acc + rgb_i*g_i
 __global__ void __launch_bounds__(256)
@@ -410,6 +469,39 @@ k_ml_composite_dist_bw(int n_rays, int K, const float* __restrict__ gRGB,
     seg_backward<true>(sig, rgbs, dl, ts, ws, nullptr, offsets[seg], counts[seg], thr,
                        RGBk[3 * seg], RGBk[3 * seg + 1], RGBk[3 * seg + 2], Ok[seg], Dk[seg], gr,
                        gg, gb, go, gd, dsig, drgb, gdist ? gdist[seg] : gdist_c, dist_k[seg]);
+}
+
+// the plain backward plus the seed gdvar[K][B] on dvar_k (rn_ml_composite_depth_bw);
+// DIST: and the distortion seed, as k_ml_composite_dist_bw
+template <bool DIST>
+__global__ void __launch_bounds__(256)
+k_ml_composite_depth_bw(int n_rays, int K, const float* __restrict__ gRGB,
+                        const float* __restrict__ gO, const float* __restrict__ gDepth,
+                        const float* __restrict__ gate, const float* __restrict__ bg,
+                        const float* __restrict__ sig, const float* __restrict__ rgbs,
+                        const float* __restrict__ dl, const float* __restrict__ ts,
+                        const int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
+                        const float* __restrict__ Ok, const float* __restrict__ Dk,
+                        const float* __restrict__ RGBk, const float* __restrict__ target_t,
+                        float clip2, const float* __restrict__ gdvar,
+                        const float* __restrict__ dvar_k, const float* __restrict__ gdist,
+                        float gdist_c, const float* __restrict__ ws,
+                        const float* __restrict__ dist_k, float thr, float* __restrict__ dsig,
+                        float* __restrict__ drgb) {
+    const int seg = blockIdx.x * (blockDim.x / RN_WAVE) + (threadIdx.x / RN_WAVE);
+    if (seg >= n_rays * K) return;
+    const int k = seg / n_rays, r = seg - k * n_rays;
+    const float g = gate[r * K + k];
+    const float gr = g * gRGB[3 * r], gg = g * gRGB[3 * r + 1], gb = g * gRGB[3 * r + 2];
+    const float bgdot = bg[0] * gRGB[3 * r] + bg[1] * gRGB[3 * r + 1] + bg[2] * gRGB[3 * r + 2];
+    const float go = g * (gO[r] - bgdot);
+    const float gd = gDepth ? gDepth[r * K + k] : 0.f;
+    float sd = 0.f, dk = 0.f;
+    if (DIST) { sd = gdist ? gdist[seg] : gdist_c; dk = dist_k[seg]; }
+    seg_backward<DIST, true>(sig, rgbs, dl, ts, DIST ? ws : nullptr, nullptr, offsets[seg],
+                             counts[seg], thr, RGBk[3 * seg], RGBk[3 * seg + 1], RGBk[3 * seg + 2],
+                             Ok[seg], Dk[seg], gr, gg, gb, go, gd, dsig, drgb, sd, dk, target_t[r],
+                             clip2, gdvar[seg], dvar_k[seg]);
 }
 
 // ---------------------------------------------------------------------------
@@ -617,6 +709,64 @@ int rn_ml_composite_dist_bw(const float* dL_drgb, const float* dL_dopacity,
         (int)n_rays, n_models, dL_drgb, dL_dopacity, dL_ddepth, dL_ddist, dL_ddist_const, gate, bg,
         sigmas, rgbs, deltas, ts, ws, counts, offsets, opacity_k, depth_k, rgb_k, dist_k,
         T_threshold, dL_dsigmas, dL_drgbs);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_ml_composite_depth_fw(const float* sigmas, const float* rgbs, const float* deltas,
+                             const float* ts, const int32_t* counts, const int32_t* offsets,
+                             int64_t n_rays, int32_t n_models, float T_threshold, int32_t* used,
+                             float* opacity_k, float* depth_k, float* rgb_k, float* ws,
+                             const float* target_t, float clip, float* dist_k, float* dvar_k,
+                             void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_models >= 1, "bad sizes");
+    RN_CHECK_ARG(clip > 0.f, "clip must be positive (INFINITY: no clip)");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(counts && offsets && used && opacity_k && depth_k && rgb_k && target_t && dvar_k,
+                 "null pointer");
+    const int nb = nblk(n_rays * n_models, 4);
+    const float clip2 = clip * clip;
+    if (dist_k)
+        k_ml_composite_depth_fw<true><<<nb, 256, 0, (hipStream_t)stream>>>(
+            (int)n_rays, n_models, sigmas, rgbs, deltas, ts, counts, offsets, T_threshold, used,
+            opacity_k, depth_k, rgb_k, ws, target_t, clip2, dist_k, dvar_k);
+    else
+        k_ml_composite_depth_fw<false><<<nb, 256, 0, (hipStream_t)stream>>>(
+            (int)n_rays, n_models, sigmas, rgbs, deltas, ts, counts, offsets, T_threshold, used,
+            opacity_k, depth_k, rgb_k, ws, target_t, clip2, nullptr, dvar_k);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_ml_composite_depth_bw(const float* dL_drgb, const float* dL_dopacity,
+                             const float* dL_ddepth, const float* gate, const float* bg,
+                             const float* sigmas, const float* rgbs, const float* deltas,
+                             const float* ts, const int32_t* counts, const int32_t* offsets,
+                             const float* opacity_k, const float* depth_k, const float* rgb_k,
+                             const float* target_t, float clip, const float* dL_ddvar,
+                             const float* dvar_k, const float* dL_ddist, float dL_ddist_const,
+                             const float* ws, const float* dist_k, int64_t n_rays,
+                             int32_t n_models, float T_threshold, float* dL_dsigmas,
+                             float* dL_drgbs, void* stream) {
+    RN_CHECK_ARG(n_rays >= 0 && n_models >= 1, "bad sizes");
+    RN_CHECK_ARG(clip > 0.f, "clip must be positive (INFINITY: no clip)");
+    if (n_rays == 0) return 0;
+    RN_CHECK_ARG(dL_drgb && dL_dopacity && gate && bg && counts && offsets && opacity_k &&
+                 depth_k && rgb_k && target_t && dL_ddvar && dvar_k, "null pointer");
+    RN_CHECK_ARG((ws != nullptr) == (dist_k != nullptr) && (dist_k || !dL_ddist),
+                 "ws and dist_k go together");
+    const int nb = nblk(n_rays * n_models, 4);
+    const float clip2 = clip * clip;
+    if (dist_k)
+        k_ml_composite_depth_bw<true><<<nb, 256, 0, (hipStream_t)stream>>>(
+            (int)n_rays, n_models, dL_drgb, dL_dopacity, dL_ddepth, gate, bg, sigmas, rgbs, deltas,
+            ts, counts, offsets, opacity_k, depth_k, rgb_k, target_t, clip2, dL_ddvar, dvar_k,
+            dL_ddist, dL_ddist_const, ws, dist_k, T_threshold, dL_dsigmas, dL_drgbs);
+    else
+        k_ml_composite_depth_bw<false><<<nb, 256, 0, (hipStream_t)stream>>>(
+            (int)n_rays, n_models, dL_drgb, dL_dopacity, dL_ddepth, gate, bg, sigmas, rgbs, deltas,
+            ts, counts, offsets, opacity_k, depth_k, rgb_k, target_t, clip2, dL_ddvar, dvar_k,
+            nullptr, 0.f, nullptr, nullptr, T_threshold, dL_dsigmas, dL_drgbs);
     RN_CHECK_LAUNCH();
     return 0;
 }

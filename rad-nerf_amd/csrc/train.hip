@@ -153,6 +153,75 @@ __global__ void k_loss_sum(const float* __restrict__ part, int n_blocks, int use
     loss_out[q] = acc;
 }
 
+// Depth supervision (rn_depth_loss), after k_nerf_loss and the guided epilogue:
+// the expected-depth term and the ray-termination second moment (dvar_k, from
+// the composite) with their seeds, added into the loss kernel's.
+// part: [blocks][2] (mean term, second-moment term), block sums by
+// a fixed xor butterfly per wave and the four waves in order
+__global__ void __launch_bounds__(256)
+k_depth_loss(int64_t B, int K, const float* __restrict__ depth, const float* __restrict__ gate,
+             const float* __restrict__ dvar_k, const float* __restrict__ target_t,
+             const float* __restrict__ ray_weight, float lambda_d, float lambda_v,
+             float* __restrict__ part, float* __restrict__ d_depth, float* __restrict__ d_gate,
+             float* __restrict__ d_dvar) {
+    __shared__ float red[2][256 / RN_WAVE];
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    float l_d = 0.f, l_v = 0.f;
+    if (r < B) {
+        const float z = target_t[r];
+        const bool m = z > 0.f;
+        const float rw = ray_weight ? ray_weight[r] : 1.0f;
+        if (lambda_d > 0.f && m) {
+            float mean_d = 0.f;
+            for (int k = 0; k < K; ++k) mean_d += gate[r * K + k] * depth[r * K + k];
+            const float e = mean_d - z;
+            l_d = lambda_d * (e * e);
+            const float s = ((2.0f * lambda_d / (float)B) * e) * rw;
+            for (int k = 0; k < K; ++k) {
+                const float g = gate[r * K + k], D = depth[r * K + k];
+                d_depth[r * K + k] += s * g;
+                d_gate[r * K + k] += s * D;
+            }
+        }
+        if (dvar_k) {
+            const float s = m && lambda_v > 0.f ? (lambda_v / (float)B) * rw : 0.f;
+            float acc = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float g = gate[r * K + k], V = dvar_k[(int64_t)k * B + r];
+                if (m) acc += g * V;
+                d_dvar[(int64_t)k * B + r] = s * g;
+                if (s != 0.f) d_gate[r * K + k] += s * V;
+            }
+            l_v = lambda_v * acc;
+        }
+    }
+    const int lane = rn_lane(), wid = threadIdx.x / RN_WAVE;
+    float v[2] = {l_d, l_v};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        float x = v[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+        if (lane == 0) red[q][wid] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        float x = 0.f;
+        for (int w = 0; w < (int)(blockDim.x / RN_WAVE); ++w) x += red[threadIdx.x][w];
+        part[2 * (size_t)blockIdx.x + threadIdx.x] = x;
+    }
+}
+
+// the blocks' partial sums in block order, one thread per term
+__global__ void k_depth_loss_sum(const float* __restrict__ part, int n_blocks,
+                                 float* __restrict__ loss_out) {
+    const int q = threadIdx.x;
+    if (q >= 2) return;
+    float acc = 0.f;
+    for (int b = 0; b < n_blocks; ++b) acc += part[2 * (size_t)b + q];
+    loss_out[q] = acc;
+}
+
 // out[i] = (...((out[i] + part[0][i]) + part[1][i]) + ...) + part[n_slots - 1][i]:
 // one thread per i, plain fp32 adds in ascending slot order (the order is the
 // contract: include/radnerf.h), loads coalesced over i
@@ -415,6 +484,26 @@ int rn_nerf_loss_routed_det(const float* rgb, const float* target_rgb, const flo
         lambda_opacity, lambda_cv, lambda_dm, part, dL_drgb, dL_dopacity, dL_ddepth, dL_dgate);
     RN_CHECK_LAUNCH();
     k_loss_sum<<<1, 64, 0, (hipStream_t)stream>>>(part, nb, use_cv, loss_out);
+    RN_CHECK_LAUNCH();
+    return 0;
+}
+
+int rn_depth_loss(const float* depth, const float* gate, const float* dvar_k,
+                  const float* target_t, const float* ray_weight, int64_t n_rays,
+                  int32_t n_models, float lambda_depth, float lambda_depth_var, float* loss_out,
+                  float* part, float* dL_ddepth, float* dL_dgate, float* dL_ddvar, void* stream) {
+    RN_CHECK_ARG(n_rays >= 1 && n_models >= 1, "bad sizes");
+    RN_CHECK_ARG(nblk(n_rays, 256) <= 0x7fffffff / 2, "too many rays");
+    RN_CHECK_ARG(depth && gate && target_t && loss_out && part && dL_ddepth && dL_dgate,
+                 "null pointer");
+    RN_CHECK_ARG((dvar_k == nullptr) == (dL_ddvar == nullptr),
+                 "dvar_k and dL_ddvar must be given together");
+    const int nb = nblk(n_rays, 256);
+    k_depth_loss<<<nb, 256, 0, (hipStream_t)stream>>>(
+        n_rays, n_models, depth, gate, dvar_k, target_t, ray_weight, lambda_depth,
+        lambda_depth_var, part, dL_ddepth, dL_dgate, dL_ddvar);
+    RN_CHECK_LAUNCH();
+    k_depth_loss_sum<<<1, 64, 0, (hipStream_t)stream>>>(part, nb, loss_out);
     RN_CHECK_LAUNCH();
     return 0;
 }

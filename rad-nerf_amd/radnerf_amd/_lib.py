@@ -61,6 +61,12 @@ SIGNATURES = {
     "rn_ml_composite_dist_fw": [P, P, P, P, P, P, I64, I32, F32, P, P, P, P, P, P, P],
     "rn_ml_composite_dist_bw": [P, P, P, P, F32, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I32,
                                 F32, P, P, P],
+    # depth supervision (FusedMLRenderer.forward(depth_target=), sampler.TrainDepths)
+    "rn_ml_composite_depth_fw": [P, P, P, P, P, P, I64, I32, F32, P, P, P, P, P, P, F32, P, P, P],
+    "rn_ml_composite_depth_bw": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, F32, P, P, P, F32,
+                                 P, P, I64, I32, F32, P, P, P],
+    "rn_gather_depth": [P, I32, I64, I64, F32, I32, P, P, P, I64, P, P],
+    "rn_depth_loss": [P, P, P, P, P, I64, I32, F32, F32, P, P, P, P, P, P],
     "rn_field_fwd": [P, P, I64, P, P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, I32, P],
     "rn_field_bwd": [P, P, I64, P, P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, P,
                      I32, P],

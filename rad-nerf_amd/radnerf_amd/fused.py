@@ -82,6 +82,42 @@ def route_params(fn, G, gate_topk=None, gate_min=0.0, renormalize=False, always=
     return k, tau, renorm
 
 
+def check_depth_weights(fn, lambda_depth=0.0, lambda_depth_var=0.0, depth_clip=float("inf")):
+    """The depth terms' weights and clip: whether any term is on.  ValueError
+    naming the argument for a negative or NaN lambda or a clip that is not > 0
+    (inf: no clip)."""
+    for name, lam in (("lambda_depth", lambda_depth), ("lambda_depth_var", lambda_depth_var)):
+        if not float(lam) >= 0.0:
+            raise ValueError(f"{fn}: {name} must be >= 0, got {lam!r}")
+    if not float(depth_clip) > 0.0:
+        raise ValueError(f"{fn}: depth_clip must be > 0 (inf: no clip), got {depth_clip!r}")
+    return float(lambda_depth) > 0.0 or float(lambda_depth_var) > 0.0
+
+
+def check_depth_args(fn, n_rays, target, lambda_depth=0.0, lambda_depth_var=0.0,
+                     depth_clip=float("inf"), device=None):
+    """The depth supervision of a step from its arguments: whether any term is
+    on.  ValueError for what check_depth_weights refuses, a lambda > 0 without
+    targets, targets that are not (n_rays,) fp32 or -- with `device`, the rays'
+    -- not on it (the kernels take device pointers); any stride is accepted,
+    the callers make the targets contiguous.  Touches no library and allocates
+    nothing."""
+    on = check_depth_weights(fn, lambda_depth, lambda_depth_var, depth_clip)
+    if on and target is None:
+        raise ValueError(f"{fn}: lambda_depth / lambda_depth_var > 0 need depth targets "
+                         "(one ray parameter per ray; <= 0 where there is no measurement)")
+    if target is not None:
+        if not torch.is_tensor(target) or tuple(target.shape) != (int(n_rays),) \
+                or target.dtype != torch.float32:
+            raise ValueError(f"{fn}: depth targets must be a ({int(n_rays)},) fp32 tensor, got "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target)}"
+                             f"{' ' + str(target.dtype) if torch.is_tensor(target) else ''}")
+        if device is not None and target.device != torch.device(device):
+            raise ValueError(f"{fn}: depth targets must be on the rays' device {device}, got "
+                             f"{target.device}")
+    return on
+
+
 class Workspace:
     """Persistent device buffers for one (B, K) configuration."""
 
@@ -120,6 +156,7 @@ class Workspace:
         self._bwd_scratch = None
         self._chunks = self._chunk_desc = None
         self._dist_k = None         # per-segment distortion loss (distortion steps only)
+        self._dvar_k = None         # per-segment depth second moment (depth steps only)
         # allocated by the first backward that needs them: integer-grid and
         # fixed-point state (fx_i: the current scale row), the binned scatter's
         # pool and read-back ring, the deterministic slots, the input gradients
@@ -153,6 +190,15 @@ class Workspace:
         if self._dist_k is None:
             self._dist_k = torch.empty(self.K, self.B, device=self.device, dtype=torch.float32)
         return self._dist_k
+
+    @property
+    def dvar_k(self):
+        """[K][B] second moment of each (sub-NeRF, ray) segment's weights about
+        the ray's depth target, written by rn_ml_composite_depth_fw and read
+        by its backward; allocated by the first depth-supervised step."""
+        if self._dvar_k is None:
+            self._dvar_k = torch.empty(self.K, self.B, device=self.device, dtype=torch.float32)
+        return self._dvar_k
 
     def chunk_list(self, max_chunk, min_chunk, head_chunks=0, balance_blocks=0):
         """rn_bwd_plan's chunk list, sized for the workspace capacity."""
@@ -454,6 +500,7 @@ class FusedMLRenderer:
         # level forward's input, the gate's side stream, fx_f32_levels as a tensor
         self._plan_key = self._side_stream = None
         self._prep_ready = self._dist_forward = False
+        self._depth_forward = None
         # measurement and tests only (tools/routed_step.py's all-live overhead
         # leg, the all-live identity test): run the routed launches (selection,
         # list march, routing backward) even when the arguments keep every pair
@@ -464,6 +511,9 @@ class FusedMLRenderer:
         # renormalize) as checked; the backward follows it
         self._routed = None
         self._f32_idx = (None, None)
+
+    # a layout that cannot supervise depth names the reason here (pinned.py)
+    _NO_DEPTH = None
 
     _NO_DET = ("FusedMLRenderer(deterministic=True) needs the merged backward (1 to 8 sub-NeRFs, "
                "merged_bwd on): the per-model backward scatters the grid gradient and dW with "
@@ -570,8 +620,14 @@ class FusedMLRenderer:
 
     def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4,
                 exp_step_factor=0.0, distortion=False, gate_topk=None, gate_min=0.0,
-                renormalize=False):
-        """distortion: the composite also writes each segment's Mip-NeRF 360
+                renormalize=False, depth_target=None, depth_clip=float("inf")):
+        """depth_target ((B,) fp32: the ray parameter at which each ray should
+        terminate, <= 0 where there is no measurement): the composite also
+        writes each segment's second moment about it, sum w min((t - z)^2,
+        depth_clip^2), into ws.dvar_k (rn_ml_composite_depth_fw; every other
+        output is the plain kernel's -- with distortion, the distortion
+        kernel's), for backward(dL_ddvar=...).
+        distortion: the composite also writes each segment's Mip-NeRF 360
         distortion loss into ws.dist_k (rn_ml_composite_dist_fw; every other
         output is the plain kernel's), for backward(dL_ddist=...).
         gate_topk / gate_min / renormalize: routed training -- rn_gate_select's
@@ -583,6 +639,8 @@ class FusedMLRenderer:
         m, g, w, L = self.model, self.gate, self.ws, lib()
         B, K, G = rays_o.shape[0], m.size, g.out_dim     # K rendered here, G gated
         assert B == w.B and noise.shape == (K, B)
+        check_depth_args("FusedMLRenderer.forward", B, depth_target, depth_clip=depth_clip,
+                         device=rays_o.device)
         routed = self._routed = self.route_params(gate_topk, gate_min, renormalize)
         st = _stream(rays_o.device)
         out_gate = torch.empty(B, G, device=rays_o.device)
@@ -645,7 +703,15 @@ class FusedMLRenderer:
                 float(T_threshold), w.used.data_ptr(), w.opacity_k.data_ptr(),
                 w.depth_k.data_ptr(), w.rgb_k.data_ptr(), w.ws.data_ptr())
         self._dist_forward = bool(distortion)       # dist_k holds this step's losses
-        if distortion:
+        # dvar_k holds this step's moments about (target, clip)
+        self._depth_forward = None
+        if depth_target is not None:
+            depth_target = depth_target.contiguous()
+            self._depth_forward = (depth_target, float(depth_clip))
+            self._ev("composite_depth_fw", L.ml_composite_depth_fw, *comp,
+                     depth_target.data_ptr(), float(depth_clip),
+                     w.dist_k.data_ptr() if distortion else None, w.dvar_k.data_ptr(), st)
+        elif distortion:
             self._ev("composite_dist_fw", L.ml_composite_dist_fw, *comp, w.dist_k.data_ptr(), st)
         else:
             self._ev("composite_fw", L.ml_composite_fw, *comp, st)
@@ -943,12 +1009,17 @@ class FusedMLRenderer:
     # ----------------------------------------------------------------- backward
     def backward(self, rays_o, rays_d, gate_in2, gate, bg, dL_drgb, dL_dopacity, dL_ddepth,
                  dL_dgate_ext=None, T_threshold=1e-4, grid_grad=None, mlp_grad=None,
-                 gate_grad=None, dL_ddist=None):
+                 gate_grad=None, dL_ddist=None, dL_ddvar=None, dL_dgate_used=None):
         """Accumulates into grid_grad / mlp_grad / gate_grad (zero-initialised
         by the caller or allocated here) and returns them.  dL_ddist: the seed
         on the per-segment distortion loss of a forward(distortion=True) --
         a [K][B] fp32 tensor, or a number for the same seed on every segment;
-        None runs the plain composite backward."""
+        None runs the plain composite backward.  dL_ddvar: the seed on
+        ws.dvar_k of a forward(depth_target=...), a [K][B] fp32 tensor
+        (rn_ml_composite_depth_bw; with dL_ddist as well, both terms in one
+        launch).  dL_dgate_used ((B, G), a routed step): a seed on the gate the
+        render was combined with, added before the routing's backward;
+        dL_dgate_ext stays the seed on the softmax gate."""
         m, g, w, L = self.model, self.gate, self.ws, lib()
         B, K, G = rays_o.shape[0], m.size, g.out_dim
         dev = rays_o.device
@@ -960,6 +1031,8 @@ class FusedMLRenderer:
         dgate = self._dgate(B, G)
         self._ev("combine_bw", L.ml_combine_bw, dL_drgb.data_ptr(), dL_dopacity.data_ptr(),
                  ok.data_ptr(), rk.data_ptr(), bg.data_ptr(), B, G, dgate.data_ptr(), st)
+        if dL_dgate_used is not None:
+            dgate.add_(dL_dgate_used)
         if self._routed is not None:
             # through gate_used = select(gate), the selection held constant:
             # dead pairs 0 (combine_bw leaves bg . dL_drgb there), live pairs
@@ -1013,7 +1086,32 @@ class FusedMLRenderer:
             gate_bwd(side)
         gate_k = self._local_cols(gate)
         ddepth_k = None if dL_ddepth is None else self._local_cols(dL_ddepth)
-        if dL_ddist is None:
+        if dL_ddvar is not None:
+            if self._depth_forward is None:
+                raise RuntimeError("backward(dL_ddvar=...): the forward of this step ran "
+                                   "without depth_target")
+            if dL_ddist is not None and not self._dist_forward:
+                raise RuntimeError("backward(dL_ddist=...): the forward of this step ran "
+                                   "without distortion=True")
+            assert dL_ddvar.shape == (K, B) and dL_ddvar.dtype == torch.float32 \
+                and dL_ddvar.is_contiguous()
+            target, clip = self._depth_forward
+            seed = torch.is_tensor(dL_ddist)
+            if seed:
+                assert dL_ddist.shape == (K, B) and dL_ddist.dtype == torch.float32 \
+                    and dL_ddist.is_contiguous()
+            dist = dL_ddist is not None
+            self._ev("composite_depth_bw", L.ml_composite_depth_bw, dL_drgb.data_ptr(),
+                     dL_dopacity.data_ptr(), None if ddepth_k is None else ddepth_k.data_ptr(),
+                     gate_k.data_ptr(), bg.data_ptr(), w.sigma.data_ptr(), w.rgb.data_ptr(),
+                     w.deltas.data_ptr(), w.ts.data_ptr(), w.counts.data_ptr(),
+                     w.offsets.data_ptr(), w.opacity_k.data_ptr(), w.depth_k.data_ptr(),
+                     w.rgb_k.data_ptr(), target.data_ptr(), clip, dL_ddvar.data_ptr(),
+                     w.dvar_k.data_ptr(), dL_ddist.data_ptr() if seed else None,
+                     float(dL_ddist) if dist and not seed else 0.0,
+                     w.ws.data_ptr() if dist else None, w.dist_k.data_ptr() if dist else None,
+                     B, K, float(T_threshold), w.dsigma.data_ptr(), w.drgb.data_ptr(), st)
+        elif dL_ddist is None:
             self._ev("composite_bw", L.ml_composite_bw, dL_drgb.data_ptr(), dL_dopacity.data_ptr(),
                      None if ddepth_k is None else ddepth_k.data_ptr(), gate_k.data_ptr(),
                      bg.data_ptr(), w.sigma.data_ptr(), w.rgb.data_ptr(),
@@ -1086,7 +1184,8 @@ class FusedMLRenderer:
                    lambda_cv_importance=0.0, lambda_depth_mutual=0.0, T_threshold=1e-4,
                    exp_step_factor=0.0, grid_grad=None, mlp_grad=None, gate_grad=None,
                    lambda_distortion=0.0, input_grad=False, gate_topk=None, gate_min=0.0,
-                   renormalize=False, ray_weight=None, guided=None):
+                   renormalize=False, target_depth=None, lambda_depth=0.0,
+                   lambda_depth_var=0.0, depth_clip=float("inf"), ray_weight=None, guided=None):
         """render -> NeRFLoss -> backward of train_ml.py:179-192 as one launch
         chain: the fused loss kernel writes the backward seeds directly.
         Returns ({term: mean}, (grid_grad, mlp_grad, gate_grad)); gradients are
@@ -1115,14 +1214,40 @@ class FusedMLRenderer:
         terms: they are the means a log compares across runs.  guided: a
         (GuidedSampler, cell_idx) pair; the same launch then records each
         ray's unweighted squared rgb error in the sampler's accumulators.
-        ray_weight=None launches nothing extra."""
-        from .losses import fused_nerf_loss
+        ray_weight=None launches nothing extra.
+        target_depth ((B,) fp32: the ray parameter each ray should terminate
+        at, <= 0 where there is no measurement) with lambda_depth > 0 adds
+        terms["depth"] = lambda_depth / B sum_r m_r (sum_k g D - z)^2 (m_r =
+        z_r > 0), with lambda_depth_var > 0 terms["depth_var"] = lambda_depth_var
+        / B sum_r m_r sum_k g V: V the second moment of each segment's weights
+        about z (each (t - z)^2 clipped at depth_clip^2), formed and
+        differentiated inside the composite kernels (rn_ml_composite_depth_fw /
+        _bw), g the gate the render was combined with.  One launch after the
+        loss and the guided epilogue (rn_depth_loss) adds both terms' seeds,
+        the gate's included, each multiplied by ray_weight; the terms are
+        ordered sums in either mode.  ValueError before any launch for a
+        lambda > 0 without targets, targets that are not (B,) fp32, or
+        depth_clip <= 0.  Both lambdas 0: nothing is launched or returned
+        beyond the step without them."""
+        from .losses import fused_depth_loss, fused_nerf_loss
         if guided is not None and ray_weight is None:
             raise ValueError("train_step: guided=(sampler, cell_idx) needs ray_weight")
+        depth_on = check_depth_args("train_step", rays_o.shape[0], target_depth, lambda_depth,
+                                    lambda_depth_var, depth_clip, device=rays_o.device)
+        if depth_on and self._NO_DEPTH:
+            raise NotImplementedError(self._NO_DEPTH)
+        if depth_on:
+            # one contiguous tensor for the composite and the loss: a strided
+            # view (a column of an image-shaped map) would be read as if dense
+            target_depth = target_depth.detach().contiguous()
+            if ray_weight is not None:
+                ray_weight = ray_weight.float().contiguous()
+        dvar = depth_on and lambda_depth_var > 0
         dist = lambda_distortion > 0
-        rgb, opacity, depth, gate, imp = self.forward(rays_o, rays_d, gate_in2, noise, bg,
-                                                      T_threshold, exp_step_factor, dist,
-                                                      gate_topk, gate_min, renormalize)
+        rgb, opacity, depth, gate, imp = self.forward(
+            rays_o, rays_d, gate_in2, noise, bg, T_threshold, exp_step_factor, dist, gate_topk,
+            gate_min, renormalize, **(dict(depth_target=target_depth, depth_clip=depth_clip)
+                                      if dvar else {}))
         # the step's render, for callers that log it (train_step returns the
         # loss terms and the gradients only)
         self.last_forward = {"rgb": rgb, "opacity": opacity, "depth": depth, "gate": gate,
@@ -1145,14 +1270,29 @@ class FusedMLRenderer:
                             None if gs is None else gs.acc_cnt, d_rgb, d_op, d_depth)
             if dist:
                 d_dist = (ray_weight * d_dist).expand(self.model.size, -1).contiguous()
+        extra = {}
+        if depth_on:
+            # on a routed step the terms' gate is gate_used: its seed goes in
+            # before the routing's backward, not with the softmax gate's
+            d_gate_used = d_gate if rt is None else torch.zeros_like(d_gate)
+            dterms, d_dvar = fused_depth_loss(
+                depth, gate if rt is None else rt["gate_used"], self.ws.dvar_k if dvar else None,
+                target_depth, ray_weight, lambda_depth, lambda_depth_var, d_depth, d_gate_used)
+            terms.update(dterms)
+            if dvar:
+                extra["dL_ddvar"] = d_dvar
+            if rt is not None:
+                extra["dL_dgate_used"] = d_gate_used
         if not input_grad:
             grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
-                                  d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist)
+                                  d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist,
+                                  **extra)
             return terms, grads
         saved, self.input_grad = self.input_grad, True
         try:
             grads = self.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
-                                  d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist)
+                                  d_gate, T_threshold, grid_grad, mlp_grad, gate_grad, d_dist,
+                                  **extra)
         finally:
             self.input_grad = saved
         w = self.ws
@@ -1162,9 +1302,12 @@ class FusedMLRenderer:
 class _MLRenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid_params, mlp_params, gate_params, renderer, rays_o, rays_d, gate_in2,
-                noise, bg, T_threshold, esf, distortion=False, route=(None, 0.0, False)):
-        rgb, opacity, depth, gate, imp = renderer.forward(rays_o, rays_d, gate_in2, noise, bg,
-                                                          T_threshold, esf, distortion, *route)
+                noise, bg, T_threshold, esf, distortion=False, route=(None, 0.0, False),
+                depth=None):
+        # depth: None or (target (B,), clip); the target carries no gradient
+        rgb, opacity, depth_out, gate, imp = renderer.forward(
+            rays_o, rays_d, gate_in2, noise, bg, T_threshold, esf, distortion, *route,
+            **({} if depth is None else dict(depth_target=depth[0], depth_clip=depth[1])))
         # the backward reads this step's samples from the renderer's workspace:
         # stamp it, so a second forward through the same workspace before this
         # backward is caught instead of silently differentiating the wrong step
@@ -1173,14 +1316,22 @@ class _MLRenderFn(torch.autograd.Function):
         ctx.renderer = renderer
         ctx.save_for_backward(rays_o, rays_d, gate_in2, gate, bg)
         ctx.T = T_threshold
+        ctx.extra = (bool(distortion), depth is not None)
+        out = (rgb, opacity, depth_out, gate)
         if distortion:
-            # fifth output: the per-ray distortion loss of every sub-NeRF, (B, K)
-            return rgb, opacity, depth, gate, renderer.ws.dist_k.t().contiguous()
-        return rgb, opacity, depth, gate
+            # next output: the per-ray distortion loss of every sub-NeRF, (B, K)
+            out += (renderer.ws.dist_k.t().contiguous(),)
+        if depth is not None:
+            # last output: each sub-NeRF's second moment about the target, (B, K)
+            out += (renderer.ws.dvar_k.t().contiguous(),)
+        return out
 
     @staticmethod
-    def backward(ctx, d_rgb, d_op, d_depth, d_gate, d_dist=None):
+    def backward(ctx, d_rgb, d_op, d_depth, d_gate, *d_extra):
         rays_o, rays_d, gate_in2, gate, bg = ctx.saved_tensors
+        d_extra = list(d_extra)
+        d_dist = d_extra.pop(0) if ctx.extra[0] else None
+        d_dvar = d_extra.pop(0) if ctx.extra[1] else None
         if ctx.renderer.ws.generation != ctx.generation:
             raise RuntimeError(
                 "ml_render_fused: the renderer's workspace was reused by another forward "
@@ -1195,12 +1346,14 @@ class _MLRenderFn(torch.autograd.Function):
         d_gate = None if d_gate is None else d_gate.float().contiguous()
         # the kernel's seed layout is [K][B]
         d_dist = None if d_dist is None else d_dist.float().t().contiguous()
+        if ctx.extra[1]:
+            d_dvar = z(K, B) if d_dvar is None else d_dvar.float().t().contiguous()
         r = ctx.renderer
         need_o, need_d, need_2 = ctx.needs_input_grad[4:7]
         r.input_grad = bool(need_o or need_d or need_2)
         try:
             gg, mg, ag = r.backward(rays_o, rays_d, gate_in2, gate, bg, d_rgb, d_op, d_depth,
-                                    d_gate, ctx.T, dL_ddist=d_dist)
+                                    d_gate, ctx.T, dL_ddist=d_dist, dL_ddvar=d_dvar)
         finally:
             input_grad, r.input_grad = r.input_grad, False
         do = dd = d2 = None
@@ -1209,7 +1362,7 @@ class _MLRenderFn(torch.autograd.Function):
             do = w.drays_o + w.gate_dx[:, 0:3] if need_o else None
             dd = w.drays_d.clone() if need_d else None
             d2 = w.gate_dx[:, 3:6].contiguous() if need_2 else None
-        return gg, mg, ag, None, do, dd, d2, None, None, None, None, None, None
+        return gg, mg, ag, None, do, dd, d2, None, None, None, None, None, None, None
 
 
 class _GradNotSupported(torch.autograd.Function):
@@ -1292,7 +1445,15 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     forward).  "gating_code" and "gating_importance" stay the softmax gate and
     its column sums, differentiable; "gating_used" (B, K) and "gating_live"
     (B, K) bool are added, values only.  Column i of "depth" is 0 for a dead
-    pair and independent_rgbs[i] is the background there."""
+    pair and independent_rgbs[i] is the background there.
+    depth_target= ((B,) fp32 ray parameters, <= 0: no measurement) /
+    depth_clip=: adds "depth_var", fp32 (B, K): column i the second moment of
+    sub-NeRF i's weights about the target, sum w min((t - z)^2, clip^2) (not
+    gate-weighted), computed and differentiated inside the composite kernels.
+    NeRFLoss(lambda_depth_var > 0) reads it."""
+    depth_target = kwargs.get("depth_target")
+    check_depth_args("ml_render", rays_o.shape[0], depth_target,
+                     depth_clip=kwargs.get("depth_clip", float("inf")), device=rays_o.device)
     route = (kwargs.get("gate_topk"), kwargs.get("gate_min", 0.0),
              bool(kwargs.get("renormalize", False)))
     route_params("ml_render", gating_net.out_dim, *route)     # ValueError before any launch
@@ -1315,7 +1476,13 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
     routed = r.route_params(*route) is not None
     fn_args = (model.xyz_encoder.params, model.mlp_params, gating_net.params, r, rays_o, rays_d,
                second, noise.contiguous(), bg, float(kwargs.get("T_threshold", 1e-4)), esf)
-    if distortion:
+    if depth_target is not None:
+        outs = _MLRenderFn.apply(*fn_args, distortion, route,
+                                 (depth_target.detach().contiguous(),
+                                  float(kwargs.get("depth_clip", float("inf")))))
+        rgb, opacity, depth, gate = outs[:4]
+        dist, dvar = (outs[4] if distortion else None), outs[-1]
+    elif distortion:
         rgb, opacity, depth, gate, dist = _MLRenderFn.apply(*fn_args, True, route)
     elif routed:
         rgb, opacity, depth, gate = _MLRenderFn.apply(*fn_args, False, route)
@@ -1332,6 +1499,8 @@ def ml_render_fused(model, gating_net, rays_o, rays_d, imgs_d, warmup=False, **k
            "gating_code": gate, "gating_importance": gate.sum(0)}
     if distortion:
         out["distortion"] = dist
+    if depth_target is not None:
+        out["depth_var"] = dvar
     if routed:
         rt = w.route_buffers()
         out["gating_used"] = rt["gate_used"].clone()

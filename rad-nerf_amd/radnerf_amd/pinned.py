@@ -108,10 +108,18 @@ class PinnedMLRenderer(FusedMLRenderer):
     _NO_ROUTING = ("PinnedMLRenderer: routed training (gate_topk / gate_min / renormalize) is "
                    "not supported in the sub-NeRF-per-GPU layout; use the data-parallel renderer")
 
+    # train_step(lambda_depth / lambda_depth_var > 0) raises it (fused.py)
+    _NO_DEPTH = ("PinnedMLRenderer: depth supervision (lambda_depth / lambda_depth_var, "
+                 "depth_target) is not supported in the sub-NeRF-per-GPU layout; use the "
+                 "data-parallel renderer")
+
     def forward(self, rays_o, rays_d, gate_in2, noise, bg, T_threshold=1e-4, exp_step_factor=0.0,
-                distortion=False, gate_topk=None, gate_min=0.0, renormalize=False):
+                distortion=False, gate_topk=None, gate_min=0.0, renormalize=False,
+                depth_target=None, depth_clip=float("inf")):
         if distortion:
             raise NotImplementedError(self._NO_DISTORTION)
+        if depth_target is not None:
+            raise NotImplementedError(self._NO_DEPTH)
         if route_params("PinnedMLRenderer", noise.shape[0], gate_topk, gate_min,
                         renormalize) is not None:
             raise NotImplementedError(self._NO_ROUTING)
@@ -153,10 +161,12 @@ class PinnedMLRenderer(FusedMLRenderer):
 
     def backward(self, rays_o, rays_d, gate_in2, gate, bg, dL_drgb, dL_dopacity, dL_ddepth,
                  dL_dgate_ext=None, T_threshold=1e-4, grid_grad=None, mlp_grad=None,
-                 gate_grad=None, dL_ddist=None):
+                 gate_grad=None, dL_ddist=None, dL_ddvar=None, dL_dgate_used=None):
         """mlp_grad: the full (K, FIELD_PARAMS) buffer; this rank adds its rows."""
         if dL_ddist is not None:
             raise NotImplementedError(self._NO_DISTORTION)
+        if dL_ddvar is not None or dL_dgate_used is not None:
+            raise NotImplementedError(self._NO_DEPTH)
         if self.input_grad:
             # each rank would hold the ray gradients of its own sub-NeRFs only
             raise NotImplementedError(

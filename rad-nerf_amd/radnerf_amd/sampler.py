@@ -61,6 +61,96 @@ class TrainImages:
         self.device = images.device
 
 
+DEPTH_KINDS = {"t": 0, "euclidean": 1}
+
+
+class TrainDepths:
+    """The training set's depth maps as rn_gather_depth reads them: (N, H*W)
+    uint16 (torch.uint16, or int16 storage of the same words) or float32,
+    contiguous, on the device; nothing is converted or copied.  A raw value v
+    becomes the target ray parameter of its pixel's ray: kind "t", t = v *
+    scale -- the z-depth for directions whose z is 1 and which are not
+    normalised (ray_utils.get_ray_directions), so e.g. scale = 1 / 1000 for
+    millimetre maps of a scene in metres, times the dataset's own scene scale;
+    kind "euclidean", the range along the ray, t = (v * scale) / |direction|.
+    A raw 0, a negative value or a NaN means "no measurement" (t = 0).
+    images: the TrainImages the maps belong to; their (N, H*W) must agree."""
+
+    def __init__(self, depths, scale=1.0, kind="t", images=None):
+        fn = "TrainDepths"
+        if not torch.is_tensor(depths):
+            raise ValueError(f"{fn}: depths must be a tensor, got {type(depths).__name__}")
+        if depths.ndim != 2 or depths.shape[0] < 1 or depths.shape[1] < 1:
+            raise ValueError(f"{fn}: depths must be (N, H*W), got {tuple(depths.shape)}")
+        codes = {torch.float32: 1, torch.int16: 0}
+        if hasattr(torch, "uint16"):
+            codes[torch.uint16] = 0
+        if depths.dtype not in codes:
+            raise ValueError(f"{fn}: depths must be uint16 or float32, got {depths.dtype}")
+        if not depths.is_contiguous():
+            raise ValueError(f"{fn}: depths must be contiguous")
+        if kind not in DEPTH_KINDS:
+            raise ValueError(f"{fn}: kind must be 't' or 'euclidean', got {kind!r}")
+        scale = float(scale)
+        if not (scale > 0.0 and scale < float("inf")):
+            raise ValueError(f"{fn}: scale must be a positive finite number, got {scale!r}")
+        if images is not None:
+            if not isinstance(images, TrainImages):
+                raise ValueError(f"{fn}: images must be a TrainImages")
+            if (images.n_images, images.n_pix) != tuple(depths.shape):
+                raise ValueError(f"{fn}: depths {tuple(depths.shape)} do not match the images' "
+                                 f"{(images.n_images, images.n_pix)}")
+        if depths.shape[0] >= 1 << 32 or depths.shape[1] >= 1 << 32:
+            raise ValueError(f"{fn}: at most 2^32 - 1 maps and pixels per map, got "
+                             f"{tuple(depths.shape)}")
+        if not depths.is_cuda:
+            raise ValueError(f"{fn}: depths must be on the GPU, got {depths.device}")
+        if images is not None and images.device != depths.device:
+            raise ValueError(f"{fn}: depths must be on the images' device {images.device}")
+        self.depths = depths.detach()
+        self.n_images, self.n_pix = int(depths.shape[0]), int(depths.shape[1])
+        self.dtype_code = codes[depths.dtype]
+        self.scale, self.kind, self.kind_code = scale, kind, DEPTH_KINDS[kind]
+        self.device = depths.device
+
+    def check_images(self, fn, images):
+        """ValueError unless these maps have the shape and device of `images`"""
+        if (images.n_images, images.n_pix) != (self.n_images, self.n_pix):
+            raise ValueError(f"{fn}: depths {(self.n_images, self.n_pix)} do not match the "
+                             f"images' {(images.n_images, images.n_pix)}")
+        if images.device != self.device:
+            raise ValueError(f"{fn}: depths must be on the images' device {images.device}")
+
+
+def gather_depth(train_depths, directions, img_idxs, pix_idxs, out=None):
+    """The target ray parameter of each pick, (n,) fp32 (rn_gather_depth):
+    0 where the map holds no measurement.  directions (H*W, 3) as the sampler's
+    (read for kind "euclidean" only); img_idxs / pix_idxs (n,) int64, e.g. a
+    batch's; out: a (n,) fp32 buffer to overwrite."""
+    fn = "gather_depth"
+    td = train_depths
+    if not isinstance(td, TrainDepths):
+        raise ValueError(f"{fn}: train_depths must be a TrainDepths")
+    n = int(img_idxs.shape[0])
+    for name, t in (("img_idxs", img_idxs), ("pix_idxs", pix_idxs)):
+        if tuple(t.shape) != (n,) or t.dtype != torch.int64 or not t.is_contiguous() \
+                or t.device != td.device:
+            raise ValueError(f"{fn}: {name} must be ({n},) contiguous int64 on {td.device}")
+    if td.kind_code == 1:
+        _f32(fn, "directions", directions, (td.n_pix, 3))
+        if directions.device != td.device:
+            raise ValueError(f"{fn}: directions must be on {td.device}")
+    if out is None:
+        out = torch.empty(n, device=td.device, dtype=torch.float32)
+    else:
+        _f32(fn, "out", out, (n,))
+    lib().gather_depth(td.depths.data_ptr(), td.dtype_code, td.n_images, td.n_pix, td.scale,
+                       td.kind_code, directions.data_ptr() if td.kind_code == 1 else None,
+                       img_idxs.data_ptr(), pix_idxs.data_ptr(), n, out.data_ptr(),
+                       torch.cuda.current_stream(td.device).cuda_stream)
+    return out
+
+
 def _f32(fn, name, t, shape):
     if not torch.is_tensor(t) or tuple(t.shape) != shape:
         raise ValueError(f"{fn}: {name} must be {shape}, got {tuple(getattr(t, 'shape', ()))}")

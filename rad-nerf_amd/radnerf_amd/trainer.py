@@ -131,10 +131,24 @@ class Trainer:
                  bucketed=True, lambda_distortion=0.0, directions=None, poses=None,
                  optimize_ext=False, pose_lr=1e-8, img_wh=None, images=None, intrinsics=None,
                  cull_invisible=False, erode=False, deterministic=False, gate_topk=None,
-                 gate_min=0.0, renormalize=False, route_from_step=0, guided=False,
+                 gate_min=0.0, renormalize=False, route_from_step=0, depths=None,
+                 lambda_depth=0.0, lambda_depth_var=0.0, depth_clip=float("inf"), guided=False,
                  guided_tile=16, guided_uniform_frac=0.5, guided_alpha=0.5,
                  guided_refresh_every=16):
-        """gate_topk / gate_min / renormalize: routed training (FusedMLRenderer.
+        """depths / lambda_depth / lambda_depth_var / depth_clip: depth
+        supervision (DESIGN.md §4 "Depth supervision").  depths: the training
+        set's depth maps (sampler.TrainDepths, or an (N, H*W) uint16 / fp32
+        device tensor taken at scale 1, kind "t"), pixel by pixel of `images`;
+        step_sampled / fit gather each batch's target ray parameters from its
+        picks (rn_gather_depth), step and step_pixels take them from the caller
+        (target_depth=).  lambda_depth weighs the squared error of the gated
+        expected depth, lambda_depth_var the second moment of the
+        ray-termination distribution about the target (each (t - z)^2 clipped
+        at depth_clip^2); both are divided by the batch size, and a ray
+        without a measurement (target <= 0) adds nothing.  ValueError for a
+        negative lambda, depth_clip <= 0, or maps that do not match the
+        images, before anything is allocated.
+        gate_topk / gate_min / renormalize: routed training (FusedMLRenderer.
         forward; DESIGN.md §4 "Routed training") -- every step from global_step
         route_from_step on marches and differentiates only the (ray, sub-NeRF)
         pairs the gate keeps; the steps before it train dense, so the gate can
@@ -192,6 +206,21 @@ class Trainer:
                 raise ValueError(f"Trainer: images are {images.n_images} x {images.n_pix} pixels "
                                  f"for {poses.shape[0]} poses and {directions.shape[0]} rows of "
                                  "directions")
+        from .fused import check_depth_weights
+        check_depth_weights("Trainer", lambda_depth, lambda_depth_var, depth_clip)
+        if depths is not None:
+            from .sampler import TrainDepths
+            if images is None:
+                raise ValueError("Trainer(depths=...) needs images (and directions, poses): the "
+                                 "maps are those of the training images, pixel by pixel")
+            if not isinstance(depths, TrainDepths):
+                depths = TrainDepths(depths)
+            depths.check_images("Trainer", images)
+        self.depths = depths
+        self.depth_lambdas = dict(lambda_depth=float(lambda_depth),
+                                  lambda_depth_var=float(lambda_depth_var),
+                                  depth_clip=float(depth_clip))
+        self._target_t = None       # step_sampled()'s reused target buffer
         self.guided = None
         self._guided_args = None
         if guided:
@@ -320,11 +349,30 @@ class Trainer:
             return torch.rand(3, device=self.device)
         return torch.zeros(3, device=self.device)
 
-    def step(self, rays_o, rays_d, imgs_d, target_rgb, noise=None):
-        """One training step on this rank's rays; returns {term: mean} (this rank)."""
-        return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, None)
+    def _depth_on(self):
+        # (a trainer assembled before the option existed has no attribute)
+        d = getattr(self, "depth_lambdas", None)
+        return d is not None and (d["lambda_depth"] > 0 or d["lambda_depth_var"] > 0)
 
-    def step_pixels(self, img_idxs, pix_idxs, target_rgb, noise=None):
+    def _depth_args(self, fn, n_rays, target_depth):
+        """train_step's depth arguments for this step: none with both lambdas
+        0 (the targets are then not looked at); ValueError for a lambda > 0
+        without targets or targets that are not (n_rays,) fp32"""
+        if not self._depth_on():
+            return {}
+        from .fused import check_depth_args
+        check_depth_args(fn, n_rays, target_depth, **self.depth_lambdas,
+                         device=getattr(self, "device", None))
+        return dict(target_depth=target_depth, **self.depth_lambdas)
+
+    def step(self, rays_o, rays_d, imgs_d, target_rgb, noise=None, target_depth=None):
+        """One training step on this rank's rays; returns {term: mean} (this rank).
+        target_depth ((B,) fp32 ray parameters, <= 0: no measurement): the
+        depth terms' targets (Trainer(lambda_depth=, lambda_depth_var=))."""
+        depth = self._depth_args("Trainer.step", rays_o.shape[0], target_depth)
+        return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, None, depth=depth)
+
+    def step_pixels(self, img_idxs, pix_idxs, target_rgb, noise=None, target_depth=None):
         """One training step on this rank's (image, pixel) picks of the
         trainer's cameras (train_ml.py:84-96).  With optimize_ext the rays
         come from the refined poses (rays.pose_rays), the chain also
@@ -333,15 +381,17 @@ class Trainer:
         from . import rays as R
         if self.directions is None:
             raise ValueError("Trainer.step_pixels needs Trainer(directions=..., poses=...)")
+        depth = self._depth_args("Trainer.step_pixels", img_idxs.shape[0], target_depth)
         img_idxs = img_idxs.to(self.device, torch.int64).contiguous()
         pix_idxs = pix_idxs.to(self.device, torch.int64).contiguous()
         if not self.optimize_ext:
             rays_o, rays_d, imgs_d = R.batch_rays(self.directions, self.poses, img_idxs, pix_idxs)
-            return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, None)
+            return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, None, depth=depth)
         with torch.no_grad():
             rays_o, rays_d, imgs_d = R.pose_rays(self.directions, self.poses, self.dR, self.dT,
                                                  img_idxs, pix_idxs, mean_dir=self.mean_dir)
-        return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, (img_idxs, pix_idxs))
+        return self._step(rays_o, rays_d, imgs_d, target_rgb, noise, (img_idxs, pix_idxs),
+                          depth=depth)
 
     def step_sampled(self, noise=None):
         """One training step on a batch the trainer draws itself from its
@@ -357,6 +407,9 @@ class Trainer:
         if self.images is None:
             raise ValueError("Trainer.step_sampled needs Trainer(images=..., directions=..., "
                              "poses=...)")
+        if self._depth_on() and self.depths is None:
+            raise ValueError("Trainer.step_sampled: lambda_depth / lambda_depth_var > 0 need "
+                             "Trainer(depths=...)")
         if self.mean_dir is None and self.gate.type == "image":
             self.mean_dir = self.directions.mean(0).contiguous()
         ext = self.optimize_ext
@@ -379,14 +432,22 @@ class Trainer:
         bg = b["bg"] if self.random_bg and self.esf != 0 else self._bg()
         weights = {} if gs is None else dict(ray_weight=b["ray_weight"],
                                              guided=(gs, b["cell_idx"]))
+        depth = {}
+        if self._depth_on():
+            # the targets of this batch's picks, whichever sampler drew them
+            from .sampler import gather_depth
+            self._target_t = gather_depth(self.depths, self.directions, b["img_idxs"],
+                                          b["pix_idxs"], out=self._target_t)
+            depth = dict(target_depth=self._target_t, **self.depth_lambdas)
         terms = self._step(b["rays_o"], b["rays_d"], b["imgs_d"], b["target"],
                            b["noise"] if noise is None else noise,
-                           (b["img_idxs"], b["pix_idxs"]) if ext else None, bg, weights)
+                           (b["img_idxs"], b["pix_idxs"]) if ext else None, bg, weights, depth)
         if gs is not None:
             self._guided_pending = True
         return terms
 
-    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks, bg=None, weights=None):
+    def _step(self, rays_o, rays_d, imgs_d, target_rgb, noise, picks, bg=None, weights=None,
+              depth=None):
         if self.global_step % self.update_interval == 0:
             rdist.update_density_grid(self.model, 0.01 * MAX_SAMPLES / 3 ** 0.5,
                                       self.global_step,
@@ -405,13 +466,13 @@ class Trainer:
                                                 bg, exp_step_factor=self.esf,
                                                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2],
                                                 **self.lambdas, **self._route_now(),
-                                                **(weights or {}))
+                                                **(weights or {}), **(depth or {}))
         else:
             from . import rays as R
             terms, _, (g_o, g_d, g_2) = self.renderer.train_step(
                 rays_o, rays_d, second, target_rgb, noise, bg, exp_step_factor=self.esf,
                 grid_grad=v[0], mlp_grad=v[1], gate_grad=v[2], input_grad=True, **self.lambdas,
-                **self._route_now(), **(weights or {}))
+                **self._route_now(), **(weights or {}), **(depth or {}))
             # the gate's second input is rays_d ("ray") or imgs_d ("image")
             if self.gate.type == "image":
                 g_i = g_2.contiguous()
@@ -452,6 +513,11 @@ class Trainer:
         return {"gate_topk": int(self.gate.out_dim), "gate_min": 0.0, "renormalize": False,
                 "route_from_step": 0}
 
+    @staticmethod
+    def _no_depth_hyper():
+        """the depth fields of a trainer without depth supervision"""
+        return {"lambda_depth": 0.0, "lambda_depth_var": 0.0, "depth_clip": float("inf")}
+
     def _route_hyper(self):
         """this trainer's (gate_topk None is all of them)"""
         k = self.gate.out_dim if self.gate_topk is None else self.gate_topk
@@ -474,6 +540,9 @@ class Trainer:
         route = self._route_hyper()
         if route != self._dense_hyper():
             h.update(route)
+        # and so do the depth terms' weights and clip
+        if self._depth_on():
+            h.update(self.depth_lambdas)
         # likewise the guided sampler's: absent from an unguided trainer's state
         gs = getattr(self, "guided", None)
         if gs is not None:
@@ -551,8 +620,9 @@ class Trainer:
         self.wait_saves()
         if not verified:
             TS.verify(state, where)
-        # a state without the routing fields was trained dense
-        dense = self._dense_hyper()
+        # a state without the routing fields was trained dense, one without
+        # the depth fields without depth supervision
+        dense = {**self._dense_hyper(), **self._no_depth_hyper()}
         TS.check_compatible({**state, "hyper": {**dense, **state.get("hyper", {})}},
                             self._structure(), {**dense, **self._hyper()}, override, where)
         m, dev = self.model, self.device
